@@ -1,6 +1,7 @@
 """PERT step-2 SVI throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 A step is one full ``svi_s.step`` of reference pert_model.py:801 on the step-2
@@ -16,6 +17,12 @@ Workload (configs[3] of BASELINE.json): synthetic
 pert_simulator-style data, 10,000 S-phase cells x 5,451 500 kb bins of
 notebooks/mcfrt.csv, 3 clones, P = 13, K = 4, g1_clones CN prior (weight 1e6).
 Strong scaling by default: the 10k cells are split over the ranks.
+
+A plain run sets up, warms up (a ~0.1 s burst of the pass's HBM streams, then the W steps),
+times the K steps and prints the result line.  ``--full`` adds everything else the benchmark
+measures, beside the timed region: the burst's figure as the pattern's HBM ceiling, the pass
+durations under HIP events in K more steps (the roofline block) and the CPU baseline.  ``--dump-outputs DIR`` writes what the timed steps left (``dump_outputs``); the
+inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -60,6 +67,7 @@ def synth(n_total: int, subdivide: int, seed: int, device, num_reads: float = 1e
     clone = np.arange(n_total) % 3
     g = torch.Generator(device=device)
     g.manual_seed(seed)
+    torch.manual_seed(seed)          # torch._standard_gamma below draws from the default generator
     cn = torch.as_tensor(prof, device=device)[:, torch.as_tensor(clone, device=device)]
     rho = torch.as_tensor(convert_rt_units(rt), device=device)
     tau = torch.rand(n_total, generator=g, device=device, dtype=torch.float64)
@@ -303,6 +311,102 @@ class HelperLoad:
                 "cells_per_s": round(self.cells / dt, 1)}
 
 
+def full_record(rec, args, shard, device, subdiv, world, kern_ms, dt_ev, ceil_ms, bpc, local_cb):
+    """The --full part of the result line (rank 0): the roofline block from the evented run's pass
+    durations, the pattern ceiling, --pmc / --profile figures, and the CPU baseline."""
+    step1 = args.fit == "step1"
+    n_local = shard.N
+    achieved = bpc * local_cb / (kern_ms * 1e-3) / 1e9
+    kname = ("obs_pair_kernel<5>" if step1 else
+             "enum3_kernel<13, 0, 5>" if args.variant == 3 else
+             "enum_dma_kernel<13, 0, 5>")
+    traffic, valu = None, None
+    if os.path.exists(args.pmc) and args.fit == "step2":
+        try:
+            pm = json.load(open(args.pmc))
+            if (pm.get("config") == args.config and int(pm.get("cells", -1)) == n_local
+                    and pm.get("kernel") == kname):
+                traffic = pm.get("hbm_bytes_per_launch")
+                valu = pm.get("valu")
+        except (OSError, ValueError):
+            traffic, valu = None, None
+    rec["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes/launch",
+                       "kernel": ("obs_kernel" if step1 else
+                                  "enum3_kernel<13, STEP, 5>" if args.variant == 3 else
+                                  "enum_dma_kernel<13, STEP, 5>"),
+                       "kernel_ms": kern_ms,
+                       "kernel_ms_events": ("HIP events on the pass's stream around every {} pass of the K steps "
+                                            "run right after the timed region (ms_per_step_evented: their wall "
+                                            "time; events in the value's region would cost ~50 us each)".format(
+                                                "" if args.event_stride <= 1 else "{}th".format(args.event_stride))),
+                       "bytes_per_cellbin": bpc,
+                       # PMC (profiles/pmc_traffic.json, tools/profile.sh): VALU issue fraction of
+                       # the same kernel -- the other roofline, not the binding one here
+                       "valu_issue_frac": (valu or {}).get("issue_frac")}
+    rec["ms_per_step_evented"] = dt_ev / args.steps * 1e3
+    if ceil_ms is not None:
+        rec["roofline"]["pattern_ceiling"] = {
+            "ms": ceil_ms, "GB/s": bpc * local_cb / (ceil_ms * 1e-3) / 1e9,
+            "kernel_frac_of_ceiling": ceil_ms / kern_ms,
+            "what": "pert_stream_ceiling: the pass's HBM streams (x, eta code, z/m/v read + written) with no "
+                    "arithmetic, same tiles, same shard, same process"}
+        rec["roofline"]["pi_placement"] = dict(shard.placement or {"candidates_ms": None},
+                                               what="PertShard.choose_pi_placement: pattern time of each "
+                                                    "z/m/v allocation tried at set-up (fastest kept)")
+    if args.fit == "step2" and args.variant == 3 and shard.fused:
+        rec["roofline"]["note"] = ("one launch per step (pert_enum_step): the pass with the reductions and "
+                                   "Adam folded in; kernel_ms is that launch")
+    if args.profile:
+        pn = profile_numbers(args.profile, kname)
+        if pn is not None:
+            tk = pn["avg_ns"] * 1e-6
+            ach_t = bpc * local_cb / (tk * 1e-3) / 1e9
+            rec["roofline"].update({
+                "trace_kernel_ms": tk, "trace_calls": pn["calls"], "frac_trace": ach_t / HBM_PEAK_GBS,
+                "frac_vs_trace": (achieved / HBM_PEAK_GBS) / (ach_t / HBM_PEAK_GBS),
+                "trace_source": os.path.relpath(args.profile, ROOT)})
+            if pn["hbm_bytes_per_launch"] is not None:
+                rec["roofline"]["traffic"] = pn["hbm_bytes_per_launch"]
+                rec["roofline"]["traffic_per_algorithmic"] = pn["hbm_bytes_per_launch"] / (bpc * local_cb)
+            p = pn["pmc"]
+            if p.get("SQ_WAVE_CYCLES"):
+                # where the pass's wave-cycles go (the three counters partition them): issuing,
+                # waiting on an instruction dependency / issue slot, waiting on memory (s_waitcnt)
+                wc = p["SQ_WAVE_CYCLES"]
+                rec["roofline"]["wave_cycles"] = {
+                    "active_inst": p.get("SQ_ACTIVE_INST_ANY", 0.0) / wc,
+                    "wait_inst": p.get("SQ_WAIT_INST_ANY", 0.0) / wc,
+                    "wait_mem": p.get("SQ_WAIT_ANY", 0.0) / wc}
+    if world == 1 and not args.no_cpu_baseline and args.fit == "step2" and args.prior == "g1_clones":
+        data = synth(max(args.cpu_cells, 3), subdiv, seed=0, device=device)
+        rec["cpu_baseline"] = cpu_baseline(data, args.cpu_cells, args.cpu_steps)
+    else:
+        rec["cpu_baseline"] = None
+
+
+DUMP_PI_BYTES = 32 << 20     # cap of the dumped pi-logit sample (the whole dump stays far below 64 MB)
+
+
+def dump_outputs(out_dir: str, shard, losses, rank: int = 0):
+    """What a caller of the timed path (PertShard.run_svi) holds after its last step, as
+    ``out_dir/<name>.npy``: the per-step losses run_svi returned (float64) and the fit state
+    it left -- every unconstrained site (float32) and, of the (L, N, P) pi logits, the
+    columns of a fixed seeded sample of cells (``pi_cells.npy`` names them, float64).  Ranks
+    above 0 of a sharded run write ``<name>.rank<r>.npy`` for their own shard."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"losses": np.asarray(losses, np.float64)}
+    cells = None
+    if shard.z_pi is not None:
+        n_pi = int(max(1, min(shard.N, 64, DUMP_PI_BYTES // (shard.L * P * 4))))
+        cells = np.sort(np.random.default_rng(0).choice(shard.N, size=n_pi, replace=False))
+        out["pi_cells"] = cells.astype(np.float64)
+    for name, a in shard.unconstrained(pi_cells=cells).items():
+        out[name] = np.ascontiguousarray(a, dtype=np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + (".rank{}".format(rank) if rank else "") + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -350,6 +454,12 @@ def main():
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
     ap.add_argument("--profile", default="", help="tools/profile.sh output dir of this command: report the "
                     "roofline fraction recomputed from its kernel trace and its PMC HBM bytes")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, measure and report everything else: the pattern's HBM ceiling, the "
+                         "pass durations under HIP events in K more steps (roofline block, --profile, --pmc) and "
+                         "the CPU baseline (--cpu-cells, --cpu-steps, --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the losses and the fit state they left as DIR/<name>.npy")
     ap.add_argument("--fullfit-c1", action="store_true",
                     help="time the configs[0] stand-in's full fit on the GPU and on the CPU oracle, then exit")
     args = ap.parse_args()
@@ -469,11 +579,16 @@ def main():
     # r05g, 1,250 cells 0.510 ms/step in the first K steps after W = 3, 0.495 in the next K;
     # r05bm, with the warmup before the burst, the value run still 1-2.4 % behind the evented
     # run after it at 1,250-2,500 cells.
-    shard.pass_events = []
-    shard.pass_event_stride = max(1, args.event_stride)
-    shard.reserve_svi(args.steps)
-    shard.pass_events = None
-    shard.reserve_svi(max(args.warmup, 0) + 2 * args.steps)   # step 1's trajectory for all three runs
+    # A plain run keeps the burst (2) as part of its warm-up (~0.1 s; without it the K = 20 value
+    # of C4 came out 0.5-0.7 % lower in 7 of 8 alternating runs on one box) but reports its figure
+    # only with --full; the second, evented run and its timing events belong to --full alone.
+    if args.full:
+        shard.pass_events = []
+        shard.pass_event_stride = max(1, args.event_stride)
+        shard.reserve_svi(args.steps)
+        shard.pass_events = None
+    # step 1's trajectory for all the runs
+    shard.reserve_svi(max(args.warmup, 0) + (2 if args.full else 1) * args.steps)
     if pg is not None:
         pg.barrier()
     ceil_ms = None
@@ -500,22 +615,26 @@ def main():
     if pg is not None:
         pg.barrier()
     dt = time.perf_counter() - t0
-    # the pass-timing run: the next K steps, HIP events around every event_stride-th pass
-    shard.pass_events = []
-    shard.pass_event_stride = max(1, args.event_stride)
-    shard.reserve_svi(args.steps)                     # (also creates the timing events)
-    if pg is not None:
-        pg.barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    shard.run_svi(args.steps, min_iter=10 ** 9, rel_tol=0.0)
-    torch.cuda.synchronize()
-    if pg is not None:
-        pg.barrier()
-    dt_ev = time.perf_counter() - t1
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in shard.pass_events]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, shard, losses, rank)
+    dt_ev, kern_ms = 0.0, 0.0
+    if args.full:
+        # the pass-timing run: the next K steps, HIP events around every event_stride-th pass
+        shard.pass_events = []
+        shard.pass_event_stride = max(1, args.event_stride)
+        shard.reserve_svi(args.steps)                     # (also creates the timing events)
+        if pg is not None:
+            pg.barrier()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        shard.run_svi(args.steps, min_iter=10 ** 9, rel_tol=0.0)
+        torch.cuda.synchronize()
+        if pg is not None:
+            pg.barrier()
+        dt_ev = time.perf_counter() - t1
+        kern_ms = float(np.mean([a.elapsed_time(b) for a, b in shard.pass_events]))
+        shard.pass_events = None
     helper_rec = helper.stop() if helper is not None else None
-    shard.pass_events = None
     t = torch.tensor([dt, kern_ms, dt_ev], dtype=torch.float64, device=device)
     if pg is not None:
         pg.all_reduce(t, op=pg.ReduceOp.MAX)
@@ -529,20 +648,6 @@ def main():
         # copies (2.5 B per fitted cell and bin)
         bpc = 2.5 if step1 else bytes_per_cellbin(P)
         local_cb = L * (n1 - n0) * (2 if step1 else 1)
-        achieved = bpc * local_cb / (kern_ms * 1e-3) / 1e9
-        kname = ("obs_pair_kernel<5>" if step1 else
-                 "enum3_kernel<13, 0, 5>" if args.variant == 3 else
-                 "enum_dma_kernel<13, 0, 5>")
-        traffic, valu = None, None
-        if os.path.exists(args.pmc) and args.fit == "step2":
-            try:
-                pm = json.load(open(args.pmc))
-                if (pm.get("config") == args.config and int(pm.get("cells", -1)) == n1 - n0
-                        and pm.get("kernel") == kname):
-                    traffic = pm.get("hbm_bytes_per_launch")
-                    valu = pm.get("valu")
-            except (OSError, ValueError):
-                traffic, valu = None, None
         rec = {
             "metric": ("enumerated ELBO+grad cell*bins/s (10k cells x 5.5k bins, 500kb)" if args.fit == "step2"
                        else "{} SVI step cell*bins/s".format(args.fit)),
@@ -558,63 +663,12 @@ def main():
                                       "events".format("_sharded" if comm is not None else "")
                                       if comm is not None or allreduce is None
                                       else "per-iteration launches from Python")},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes/launch",
-                         "kernel": ("obs_kernel" if step1 else
-                                    "enum3_kernel<13, STEP, 5>" if args.variant == 3 else
-                                    "enum_dma_kernel<13, STEP, 5>"),
-                         "kernel_ms": kern_ms,
-                         "kernel_ms_events": ("HIP events on the pass's stream around every {} pass of the K steps "
-                                              "run right after the timed region (ms_per_step_evented: their wall "
-                                              "time; events in the value's region would cost ~50 us each)".format(
-                                                  "" if args.event_stride <= 1 else "{}th".format(args.event_stride))),
-                         "bytes_per_cellbin": bpc,
-                         # PMC (profiles/pmc_traffic.json, tools/profile.sh): VALU issue fraction of
-                         # the same kernel -- the other roofline, not the binding one here
-                         "valu_issue_frac": (valu or {}).get("issue_frac")},
             "loss_first": losses[0], "loss_last": losses[-1],
         }
-        rec["ms_per_step_evented"] = dt_ev / args.steps * 1e3
         if helper_rec is not None:
             rec["helper_load"] = helper_rec
-        if ceil_ms is not None:
-            rec["roofline"]["pattern_ceiling"] = {
-                "ms": ceil_ms, "GB/s": bpc * local_cb / (ceil_ms * 1e-3) / 1e9,
-                "kernel_frac_of_ceiling": ceil_ms / kern_ms,
-                "what": "pert_stream_ceiling: the pass's HBM streams (x, eta code, z/m/v read + written) with no "
-                        "arithmetic, same tiles, same shard, same process"}
-            rec["roofline"]["pi_placement"] = dict(shard.placement or {"candidates_ms": None},
-                                                   what="PertShard.choose_pi_placement: pattern time of each "
-                                                        "z/m/v allocation tried at set-up (fastest kept)")
-        if args.fit == "step2" and args.variant == 3 and shard.fused:
-            rec["roofline"]["note"] = ("one launch per step (pert_enum_step): the pass with the reductions and "
-                                       "Adam folded in; kernel_ms is that launch")
-        if args.profile:
-            pn = profile_numbers(args.profile, kname)
-            if pn is not None:
-                tk = pn["avg_ns"] * 1e-6
-                ach_t = bpc * local_cb / (tk * 1e-3) / 1e9
-                rec["roofline"].update({
-                    "trace_kernel_ms": tk, "trace_calls": pn["calls"], "frac_trace": ach_t / HBM_PEAK_GBS,
-                    "frac_vs_trace": (achieved / HBM_PEAK_GBS) / (ach_t / HBM_PEAK_GBS),
-                    "trace_source": os.path.relpath(args.profile, ROOT)})
-                if pn["hbm_bytes_per_launch"] is not None:
-                    rec["roofline"]["traffic"] = pn["hbm_bytes_per_launch"]
-                    rec["roofline"]["traffic_per_algorithmic"] = pn["hbm_bytes_per_launch"] / (bpc * local_cb)
-                p = pn["pmc"]
-                if p.get("SQ_WAVE_CYCLES"):
-                    # where the pass's wave-cycles go (the three counters partition them): issuing,
-                    # waiting on an instruction dependency / issue slot, waiting on memory (s_waitcnt)
-                    wc = p["SQ_WAVE_CYCLES"]
-                    rec["roofline"]["wave_cycles"] = {
-                        "active_inst": p.get("SQ_ACTIVE_INST_ANY", 0.0) / wc,
-                        "wait_inst": p.get("SQ_WAIT_INST_ANY", 0.0) / wc,
-                        "wait_mem": p.get("SQ_WAIT_ANY", 0.0) / wc}
-        if world == 1 and not args.no_cpu_baseline and args.fit == "step2" and args.prior == "g1_clones":
-            data = synth(max(args.cpu_cells, 3), subdiv, seed=0, device=device)
-            rec["cpu_baseline"] = cpu_baseline(data, args.cpu_cells, args.cpu_steps)
-        else:
-            rec["cpu_baseline"] = None
+        if args.full:
+            full_record(rec, args, shard, device, subdiv, world, kern_ms, dt_ev, ceil_ms, bpc, local_cb)
         print(json.dumps(rec), flush=True)
     if comm is not None:
         comm.close()

@@ -7,9 +7,10 @@ TAG=${1:-ab}; LIB=$2
 mkdir -p gpurun_out
 OUT=gpurun_out/${TAG}_ab.log
 : > $OUT
+TMP=$(dirname $OUT)/${TAG}_ab.tmp
 row() {
   local label=$1; shift
-  timeout -k 10 150 python bench.py --steps 30 --warmup 3 --no-cpu-baseline "$@" > gpurun_out/${TAG}_ab.tmp 2>&1 || { tail -5 gpurun_out/${TAG}_ab.tmp; exit 1; }
+  timeout -k 10 150 python bench.py --full --steps 30 --warmup 3 --no-cpu-baseline "$@" > $TMP 2>&1 || { tail -5 $TMP; exit 1; }
   python -c "
 import json
 r = json.loads(open('gpurun_out/${TAG}_ab.tmp').read().strip().splitlines()[-1]); rf = r['roofline']

@@ -8,8 +8,8 @@
 #   gpu-tests        the whole -m gpu suite (as the driver runs it)
 #   tests:FILE[,..]  the named test files only (e.g. tests:test_gpu_native_comm_ranks.py)
 #   smoke            __graft_entry__.smoke()
-#   bench            the default bench line (C4, K = 200)
-#   bench-k20        the driver's settings (--steps 20 --warmup 5)
+#   bench            the default bench line with --full (C4, K = 200)
+#   bench-k20        --full --steps 20 --warmup 5
 #   bench-c5         C5 (configs[4]) with --steps 20
 #   trace            rocprofv3 --kernel-trace --stats of the default bench
 #   pmc              tools/profile.sh's counter passes (one --pmc run each) + summary
@@ -31,8 +31,8 @@ for STEP in "$@"; do
     tests:*) FILES=$(echo "${STEP#tests:}" | tr ',' '\n' | sed 's|^|tests/|' | tr '\n' ' ')
              $T 900 $PYT $FILES > "$OUT/tests_$(echo "${STEP#tests:}" | tr ',/' '__').log" 2>&1 ;;
     smoke) $T 300 python -c 'import __graft_entry__ as g; g.smoke()' > "$OUT/smoke.log" 2>&1 ;;
-    bench) $T 400 python bench.py > "$OUT/bench.log" 2>&1 ;;
-    bench-k20) $T 400 python bench.py --steps 20 --warmup 5 > "$OUT/bench_k20.log" 2>&1 ;;
+    bench) $T 400 python bench.py --full > "$OUT/bench.log" 2>&1 ;;
+    bench-k20) $T 400 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_k20.log" 2>&1 ;;
     bench-c5) $T 400 python bench.py --config c5 --steps 20 --no-cpu-baseline > "$OUT/bench_c5.log" 2>&1 ;;
     trace) (cd /tmp && export TMPDIR=/tmp && $T 400 rocprofv3 --kernel-trace --stats --output-format csv \
              -d "$OUT/trace" -o run -- python3 "$R/bench.py" --no-cpu-baseline > "$OUT/trace.log" 2>&1) ;;

@@ -11,7 +11,8 @@ mkdir -p gpurun_out
 timeout -k 10 1000 bash tools/profile.sh $TAG || exit 1
 python3 tools/pmc_summary.py gpurun_out/prof_$TAG > gpurun_out/prof_$TAG/summary.json || exit 1
 python3 tools/pmc_traffic.py gpurun_out/prof_$TAG/summary.json c4 10000 gpurun_out/prof_$TAG/pmc_traffic.json || exit 1
-timeout -k 10 300 python bench.py --profile gpurun_out/prof_$TAG --pmc gpurun_out/prof_$TAG/pmc_traffic.json \
+PROF=$(ls -d */prof_$TAG | head -1)      # where tools/profile.sh wrote
+timeout -k 10 300 python bench.py --full --profile $PROF --pmc $PROF/pmc_traffic.json \
   > gpurun_out/${TAG}_bench_profile.log 2>&1 || { tail -20 gpurun_out/${TAG}_bench_profile.log; exit 1; }
 tail -1 gpurun_out/${TAG}_bench_profile.log | cut -c1-1500
 python3 -c "

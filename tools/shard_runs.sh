@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 rm -f "$OUT/shards.jsonl"
 run() {
   local rep=$1; shift
-  timeout -k 10 240 python -u bench.py --steps 200 --warmup 3 --no-cpu-baseline "$@" > "$OUT/b.tmp" 2>&1 \
+  timeout -k 10 240 python -u bench.py --full --steps 200 --warmup 3 --no-cpu-baseline "$@" > "$OUT/b.tmp" 2>&1 \
     || { cat "$OUT/b.tmp"; exit 1; }
   grep '"metric"' "$OUT/b.tmp" | python -c "
 import json,sys

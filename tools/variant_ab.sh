@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 run() {
   local which=$1; shift
   if [ "$which" = variant ]; then export PERT_LIB=$VAR; else unset PERT_LIB; fi
-  timeout -k 10 300 python -u bench.py --no-cpu-baseline "$@" > "$OUT/b.tmp" 2>&1 || { cat "$OUT/b.tmp"; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --no-cpu-baseline "$@" > "$OUT/b.tmp" 2>&1 || { cat "$OUT/b.tmp"; exit 1; }
   grep '"metric"' "$OUT/b.tmp" | python -c "
 import json,sys
 r=json.loads(sys.stdin.read()); r['_which']='$which'; r['_args']='$*'
