@@ -382,6 +382,34 @@ int pert_tau_binarize(int32_t L, int32_t N, const float* norm, const pert_tau_pa
                       int8_t* labels, int8_t* scratch, double* means, int32_t* flags, double* frac,
                       double* minor, hipStream_t stream);
 
+/* ---- Downstream replication-timing analyses (rt_profiles.py) on the decode's rep_out.
+ * rep is uint8 [L][ldn] (0 / 1 per (bin, cell); ldn >= N a multiple of 16, the base 16-byte
+ * aligned; columns n >= N hold undefined bytes and are never counted).  group is int32 [N]: the
+ * pseudobulk row (clone) of each cell in [0, G), anything else = excluded.  Outputs are ADDED
+ * to (integer adds only: exact, identical from run to run); the caller zeroes them. */
+#define PERT_RT_MAX_GROUPS 32   /* pert_rt_tfs_hist: a tile's hours rows of every group sit in LDS */
+#define PERT_RT_MAX_EDGES 257
+
+/* bin_count uint32 [G][L]: replicated cells per bin and group (the numerators of
+ * compute_pseudobulk_rt_profiles.py:18-19 per clone; their sum over groups is the population's).
+ * cell_count uint32 [N]: replicated bins per cell, excluded cells included (the numerator of
+ * compute_cell_frac, predict_cycle_phase.py:33-38). */
+int pert_rt_counts(int32_t L, int32_t N, int32_t ldn, int32_t G, const uint8_t* rep, const int32_t* group,
+                   uint32_t* bin_count, uint32_t* cell_count, hipStream_t stream);
+
+/* calc_pct_replicated_per_time_bin (calculate_twidth.py:37-71) as counts.  hours [G][L], f10 [N]
+ * and the ascending edges [n_edges <= PERT_RT_MAX_EDGES] are float, or double when is_f64.  For
+ * every bin l and cell n < N with g = group[n] in [0, G): t = hours[g][l] - f10[n] (one
+ * subtraction in that type); the interval i with edges[i] <= t < edges[i+1] is found by
+ * comparisons against the edges alone; hist_n[i] += 1, hist_rep[i] += rep[l][n].  A t that is
+ * NaN or outside the edges counts nowhere.  per_cell 0: hist_n / hist_rep are uint32
+ * [n_edges - 1]; per_cell 1 or 2: uint32 [N][n_edges - 1] (1: a 64-cell tile of histograms in
+ * LDS per workgroup, the product path; 2: adds straight to global memory, kept for
+ * measurement; same results).  PERT_E_ARG when L * N >= 2^32 (a counter could wrap). */
+int pert_rt_tfs_hist(int32_t L, int32_t N, int32_t ldn, int32_t G, const uint8_t* rep, const int32_t* group,
+                     const void* hours, const void* f10, const void* edges, int32_t n_edges, int32_t is_f64,
+                     int32_t per_cell, uint32_t* hist_n, uint32_t* hist_rep, hipStream_t stream);
+
 /* Test-only entry points: the per-(bin, cell) arithmetic of pert_math.h evaluated on
  * the host (no GPU needed) or on the device, for the parity suite.  Not used by any
  * product path. */

@@ -6,6 +6,7 @@ module of this package is the reference module of the same name (file:line cited
 its docstring) and binds the MI355X implementation in ``scdna_replication_tools_amd``:
 the PERT fits (steps 1-3, decode) run through libpert_hip.so on the GPU; there is no
 CPU fallback.  Modules of the reference outside the PERT hot path (plotting, the
-deterministic 'cell' / 'clone' / 'bulk' levels, pseudobulk / T-width / CCC analyses,
-the Pyro simulator) are not provided.
+deterministic 'cell' / 'clone' / 'bulk' levels, CCC / SPF analyses, the Pyro simulator)
+are not provided; the pseudobulk and T-width analyses of the decode are
+(``compute_pseudobulk_rt_profiles``, ``calculate_twidth``).
 """

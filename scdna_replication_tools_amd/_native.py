@@ -22,6 +22,7 @@ MODE_STEP, MODE_GRAD, MODE_DECODE = 0, 1, 2
 MAX_K1 = 8
 MIN_P, MAX_P = 2, 16
 BLOCK = 256
+RT_MAX_GROUPS, RT_MAX_EDGES = 32, 257      # pert_rt_tfs_hist
 
 # every symbol include/pert_hip.h declares
 EXPORTED_SYMBOLS = (
@@ -32,7 +33,7 @@ EXPORTED_SYMBOLS = (
     "pert_comm_allreduce_sum_f64", "pert_svi_steps_sharded", "pert_svi_run_sharded", "pert_version",
     "pert_comm_init_host", "pert_comm_set_watchdog", "pert_comm_abort", "pert_comm_status", "pert_comm_wait_event",
     "pert_comm_inject_fault", "pert_finalize_shared", "pert_finalize_cells", "pert_comm_set_options",
-    "pert_comm_overlap", "pert_comm_allreduce_async", "pert_comm_join",
+    "pert_comm_overlap", "pert_comm_allreduce_async", "pert_comm_join", "pert_rt_counts", "pert_rt_tfs_hist",
 )
 
 # include/pert_hip.h status codes of a sharded fit's communicator
@@ -212,6 +213,9 @@ def load(path: str, gil: bool = True):
     handle.pert_selftest_enum_online_host.argtypes = [i32, i64, fp, fp, fp, fp, c_float, fp, fp, fp, fp]
     handle.pert_tau_binarize.argtypes = [i32, i32, c_void_p, POINTER(PertTauParams), c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]
+    handle.pert_rt_counts.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    handle.pert_rt_tfs_hist.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i32, i32,
+                                        i32, c_void_p, c_void_p, c_void_p]
     handle.pert_version.restype = c_char_p
     for name in EXPORTED_SYMBOLS:
         if name != "pert_version":
