@@ -410,6 +410,65 @@ int pert_rt_tfs_hist(int32_t L, int32_t N, int32_t ldn, int32_t G, const uint8_t
                      const void* hours, const void* f10, const void* edges, int32_t n_edges, int32_t is_f64,
                      int32_t per_cell, uint32_t* hist_n, uint32_t* hist_rep, hipStream_t stream);
 
+/* ---- Read-count simulator (pert_simulator.py; reference pert_simulator.py:38-282): the
+ * generative model run forwards, one Bernoulli and one negative-binomial draw per (bin, cell).
+ *
+ * Random numbers: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants
+ * 0x9E3779B9 / 0xBB67AE85), counter based.  THE COUNTER RULE: the words of a draw are
+ *   philox(counter = {bin index, low word of the global cell index, draw round,
+ *                     high word of the global cell index},
+ *          key     = {low word of seed, high word of seed ^ (stream tag * 0x9E3779B9)})
+ * so a draw depends only on the seed and on the element it belongs to (global cell index =
+ * cell0 + column), never on the grid, the tile size or which cells a launch holds: cells
+ * simulated in several launches (cell0) get the numbers one launch over all of them gives.
+ * A uniform is ((w >> 8) + 0.5) 2^-24 rounded to fp32 and kept below 1 (the one value that
+ * rounds to 1.0 becomes 1 - 2^-24): strictly inside (0, 1).
+ * Stream PERT_SIM_TAG_CELLS (bin index 0): draw round 0 word 0 -> tau; draw round 1 + k words
+ * 0, 1 -> beta k = mean + std sqrt(-2 ln u1) cos(2 pi u2), with u = ((w >> 8) + 0.5) 2^-24 and
+ * the arithmetic in fp64, rounded to fp32 once.
+ * Stream PERT_SIM_TAG_READS: draw round 0 word 0 -> the Bernoulli uniform (rep = u < phi);
+ * draw round j < 64 words 1, 2, 3 -> attempt j of the Gamma sampler (Box-Muller pair,
+ * acceptance uniform); draw round 64 + j words 0, 1 -> attempt j of the Poisson sampler (word 0
+ * of round 64 alone for inversion, rate < 10).  Rejection loops run at most 64 rounds; a lane
+ * that uses them up takes the rounded mean and adds 1 to `exhausted` (expected: never). */
+#define PERT_SIM_TAG_CELLS 1u
+#define PERT_SIM_TAG_READS 2u
+
+/* Test hook of the generator: out[i] (uint32 [n][4], 16-byte aligned, device) = the four words
+ * of the counter (c0, c1, c2, c3) + i, taken as a 128-bit integer with c0 lowest, under key
+ * (key0, key1).  1 <= n <= 2^31. */
+int pert_sim_raw(uint32_t key0, uint32_t key1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, int64_t n,
+                 uint32_t* out, hipStream_t stream);
+
+/* Per-cell draws of global cells [cell0, cell0 + N): tau float [N] ~ U(0, 1) (Beta(1, 1),
+ * pert_simulator.py:77; NULL: not drawn, G1/2 cells) and betas float [K1][N] (the fit's plane
+ * layout) ~ Normal(beta_means[libs[n]][k], beta_stds[libs[n]][k]) (:83); beta_means / beta_stds
+ * float [n_libs][K1], libs int32 [N]. */
+int pert_sim_cells(int32_t N, int32_t K1, int32_t n_libs, int64_t cell0, uint64_t seed, const int32_t* libs,
+                   const float* beta_means, const float* beta_stds, float* tau, float* betas, hipStream_t stream);
+
+/* The fused pass over [L][ldn] (ldn as in pert_problem) for global cells [cell0, cell0 + N)
+ * (pert_simulator.py:98-124): omega = exp(sum_k betas[k][n] gc[l]^(K - k)),
+ * phi = 1 / (1 + exp(-a (tau[n] - rho[l]))), rep ~ Bernoulli(phi), chi = cn (1 + rep),
+ * delta = max(u chi omega (1 - lamb) / lamb, 1), reads ~ NegativeBinomial(delta, probs = lamb)
+ * drawn as Poisson(Gamma(delta, scale = lamb / (1 - lamb))).  tau == NULL: the G1/2 model,
+ * rep = 0 (model_g1, :151-172; rho unused).  cn float [L][ldn], gc / rho float [L], betas float
+ * [K1][N].  Outputs: counts uint32 [L][ldn] (saturating), rep uint8 [L][ldn], p_rep float
+ * [L][ldn] = phi (NULL: skipped), all with columns [N, ldn) written as zero; colsum uint64 [N]
+ * and the word *exhausted are ADDED to by integer atomics (exact, order independent): the
+ * caller zeroes them.  Arithmetic is fp32: rates above 2^24 lose integer resolution. */
+int pert_sim_reads(int32_t L, int32_t N, int32_t ldn, int32_t K1, int64_t cell0, uint64_t seed, const float* cn,
+                   const float* gc, const float* rho, const float* tau, const float* betas, float u, float a,
+                   float lamb, uint32_t* counts, uint8_t* rep, float* p_rep, uint64_t* colsum, uint32_t* exhausted,
+                   hipStream_t stream);
+
+/* reads_norm float [L][ldn] = int64(counts / colsum * num_reads), the three operations in fp64
+ * (pert_simulator.py:245-247 on float64 tensors) -- the layout and type pert_problem.reads
+ * takes.  Columns [N, ldn), and a cell whose colsum is 0, are written as zero.  PERT_E_ARG for
+ * num_reads >= 2^24: the fp32 copy would no longer be exact. */
+int pert_sim_normalise(int32_t L, int32_t N, int32_t ldn, double num_reads, const uint32_t* counts,
+                       const uint64_t* colsum, float* reads_norm, hipStream_t stream);
+
 /* Test-only entry points: the per-(bin, cell) arithmetic of pert_math.h evaluated on
  * the host (no GPU needed) or on the device, for the parity suite.  Not used by any
  * product path. */

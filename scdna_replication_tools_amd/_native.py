@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
 LIB_NAME = "libpert_hip.so"
 DEFAULT_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -23,6 +23,7 @@ MAX_K1 = 8
 MIN_P, MAX_P = 2, 16
 BLOCK = 256
 RT_MAX_GROUPS, RT_MAX_EDGES = 32, 257      # pert_rt_tfs_hist
+SIM_TAG_CELLS, SIM_TAG_READS = 1, 2        # pert_sim_*: the stream tags of the counter rule
 
 # every symbol include/pert_hip.h declares
 EXPORTED_SYMBOLS = (
@@ -34,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "pert_comm_init_host", "pert_comm_set_watchdog", "pert_comm_abort", "pert_comm_status", "pert_comm_wait_event",
     "pert_comm_inject_fault", "pert_finalize_shared", "pert_finalize_cells", "pert_comm_set_options",
     "pert_comm_overlap", "pert_comm_allreduce_async", "pert_comm_join", "pert_rt_counts", "pert_rt_tfs_hist",
+    "pert_sim_raw", "pert_sim_cells", "pert_sim_reads", "pert_sim_normalise",
 )
 
 # include/pert_hip.h status codes of a sharded fit's communicator
@@ -216,6 +218,14 @@ def load(path: str, gil: bool = True):
     handle.pert_rt_counts.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_tfs_hist.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i32, i32,
                                         i32, c_void_p, c_void_p, c_void_p]
+    u32 = c_uint32
+    handle.pert_sim_raw.argtypes = [u32, u32, u32, u32, u32, u32, i64, c_void_p, c_void_p]
+    handle.pert_sim_cells.argtypes = [i32, i32, i32, i64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]
+    handle.pert_sim_reads.argtypes = [i32, i32, i32, i32, i64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]
+    handle.pert_sim_normalise.argtypes = [i32, i32, i32, c_double, c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_version.restype = c_char_p
     for name in EXPORTED_SYMBOLS:
         if name != "pert_version":
