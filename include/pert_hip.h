@@ -382,6 +382,64 @@ int pert_tau_binarize(int32_t L, int32_t N, const float* norm, const pert_tau_pa
                       int8_t* labels, int8_t* scratch, double* means, int32_t* flags, double* frac,
                       double* minor, hipStream_t stream);
 
+/* Threshold binarisation of RT profiles (Dileep & Gilbert; binarize_rt_profiles.py:44-117) for
+ * every cell of one length in ONE launch, one workgroup per cell, in fp64, on the raw
+ * (unstandardised) profile: GaussianMixture(n_components=2, random_state=0) as sklearn runs it on
+ * float64 data (KMeans tolerance, centring, k-means++, Lloyd, EM, fit_predict's final E step), the
+ * levels (GMM means, or percentiles chosen by the biased skew), and the scan of the 100 fixed
+ * thresholds for the first least Manhattan distance.  Every sum is a fixed-order block sum, so
+ * reruns are bit-identical.  The margins are those of an fp64-vs-fp64 comparison (another
+ * summation order); a decision within its margin sets a bit of flags and the caller recomputes
+ * that cell on the host (binarize.py). */
+#define PERT_BIN_THRESHOLDS 100
+typedef struct {
+  int32_t first;                   /* k-means++ first centre index (RandomState(0) draw at this L) */
+  int32_t lloyd_max_iter;          /* 300 */
+  int32_t em_max_iter;             /* 100 */
+  int32_t q_lo[5], q_hi[5];        /* np.percentile 'linear' at q = .05 .25 .5 .75 .95 */
+  int32_t pad_;
+  double q_t[5];
+  double u[2];                     /* the two local-trial uniforms of k-means++ */
+  double em_tol;                   /* 1e-3 */
+  double reg_covar;                /* 1e-6 */
+  double mean_gap;                 /* MEAN_GAP_THRESH */
+  double early_skew, late_skew;    /* EARLY_S_SKEW_THRESH, LATE_S_SKEW_THRESH */
+  double thresh[PERT_BIN_THRESHOLDS];  /* np.linspace(-3, 3, 100), the caller's bits */
+  /* margins */
+  double pp_margin;                /* k-means++ draw / choice, relative to the potential */
+  double tie_margin;               /* a Lloyd assignment on the decision boundary, relative */
+  double lloyd_margin;             /* Lloyd centre shift vs tol, relative to tol */
+  double em_margin;                /* EM |lower-bound change| vs em_tol, absolute */
+  double gap_margin;               /* |mean gap - mean_gap|, relative to max(1, |mu0| + |mu1|) */
+  double skew_margin;              /* skew vs its thresholds, absolute */
+  double resp_margin;              /* final E step's two log responsibilities, relative to 1 + |l0| + |l1| */
+  double thresh_margin;            /* |x - chosen threshold|, absolute */
+  double dist_margin;              /* another threshold's distance vs the least, relative to least + L max|level| */
+} pert_bin_params;
+
+#define PERT_BIN_F_PP 1        /* k-means++ draw or choice */
+#define PERT_BIN_F_LLOYD 2     /* Lloyd: shift-vs-tol test, or a point on the assignment boundary */
+#define PERT_BIN_F_EM 4        /* EM stopping test */
+#define PERT_BIN_F_LEVELS 8    /* mean-gap or skew test */
+#define PERT_BIN_F_RESP 16     /* a gmm_state whose two responsibilities are within margin */
+#define PERT_BIN_F_POINT 32    /* a point within margin of the chosen threshold */
+#define PERT_BIN_F_SCAN 64     /* a threshold that binarises differently, its distance within margin of the least */
+
+/* x: double [N][L], one contiguous row per cell (device).  Outputs (device, the caller's):
+ *   means, covs double [N][2]   GMM means and variances (reg_covar included), sklearn's component
+ *                               order (component 0 grew from the k-means++ first centre), unsorted
+ *   gmm_state int8 [N][L]       argmax of the final E step (also the Lloyd label workspace)
+ *   rt_state  uint8 [N][L]      x > chosen threshold (also Lloyd's previous-label workspace)
+ *   dist double [N][100]        Manhattan distance per threshold
+ *   best int32 [N]              index of the chosen threshold (first strict minimum)
+ *   n_rep int32 [N]             replicated bins
+ *   flags int32 [N]             PERT_BIN_F_* bits
+ * PERT_E_ARG for L < 2, N < 1, a null buffer or percentile / first-centre indices outside [0, L).
+ * Allocates nothing. */
+int pert_rt_binarize(int32_t L, int32_t N, const double* x, const pert_bin_params* p, double* means,
+                     double* covs, int8_t* gmm_state, uint8_t* rt_state, double* dist, int32_t* best,
+                     int32_t* n_rep, int32_t* flags, hipStream_t stream);
+
 /* ---- Downstream replication-timing analyses (rt_profiles.py) on the decode's rep_out.
  * rep is uint8 [L][ldn] (0 / 1 per (bin, cell); ldn >= N a multiple of 16, the base 16-byte
  * aligned; columns n >= N hold undefined bytes and are never counted).  group is int32 [N]: the

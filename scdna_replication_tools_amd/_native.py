@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = (
     "pert_comm_init_host", "pert_comm_set_watchdog", "pert_comm_abort", "pert_comm_status", "pert_comm_wait_event",
     "pert_comm_inject_fault", "pert_finalize_shared", "pert_finalize_cells", "pert_comm_set_options",
     "pert_comm_overlap", "pert_comm_allreduce_async", "pert_comm_join", "pert_rt_counts", "pert_rt_tfs_hist",
-    "pert_sim_raw", "pert_sim_cells", "pert_sim_reads", "pert_sim_normalise",
+    "pert_sim_raw", "pert_sim_cells", "pert_sim_reads", "pert_sim_normalise", "pert_rt_binarize",
 )
 
 # include/pert_hip.h status codes of a sharded fit's communicator
@@ -95,6 +95,21 @@ class PertTauParams(ctypes.Structure):
                 ("em_margin", c_double), ("em_tol", c_double), ("reg_covar", c_double), ("mean_gap", c_double),
                 ("early_skew", c_double), ("late_skew", c_double), ("fragile_abs", c_double),
                 ("level_margin", c_double), ("eps32", c_double)]
+
+
+BIN_THRESHOLDS = 100                       # pert_rt_binarize: np.linspace(-3, 3, 100)
+# pert_rt_binarize's flag bits (PERT_BIN_F_*)
+BIN_F_PP, BIN_F_LLOYD, BIN_F_EM, BIN_F_LEVELS, BIN_F_RESP, BIN_F_POINT, BIN_F_SCAN = 1, 2, 4, 8, 16, 32, 64
+
+
+class PertBinParams(ctypes.Structure):
+    _fields_ = [("first", c_int32), ("lloyd_max_iter", c_int32), ("em_max_iter", c_int32),
+                ("q_lo", c_int32 * 5), ("q_hi", c_int32 * 5), ("pad_", c_int32), ("q_t", c_double * 5),
+                ("u", c_double * 2), ("em_tol", c_double), ("reg_covar", c_double), ("mean_gap", c_double),
+                ("early_skew", c_double), ("late_skew", c_double), ("thresh", c_double * BIN_THRESHOLDS),
+                ("pp_margin", c_double), ("tie_margin", c_double), ("lloyd_margin", c_double),
+                ("em_margin", c_double), ("gap_margin", c_double), ("skew_margin", c_double),
+                ("resp_margin", c_double), ("thresh_margin", c_double), ("dist_margin", c_double)]
 
 
 class PertAdamHparams(ctypes.Structure):
@@ -215,6 +230,8 @@ def load(path: str, gil: bool = True):
     handle.pert_selftest_enum_online_host.argtypes = [i32, i64, fp, fp, fp, fp, c_float, fp, fp, fp, fp]
     handle.pert_tau_binarize.argtypes = [i32, i32, c_void_p, POINTER(PertTauParams), c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]
+    handle.pert_rt_binarize.argtypes = [i32, i32, c_void_p, POINTER(PertBinParams), c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_counts.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_tfs_hist.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i32, i32,
                                         i32, c_void_p, c_void_p, c_void_p]

@@ -1,19 +1,22 @@
-"""Drop-in ``scRT`` orchestrator (reference scdna_replication_tools/infer_scRT.py:25-168),
-PERT level only.
+"""Drop-in ``scRT`` orchestrator (reference scdna_replication_tools/infer_scRT.py:25-290): the
+PERT level and the deterministic bulk level.
 
 ``scRT(cn_s, cn_g1, ...).infer(level='pert')`` (or 'pyro') computes the consensus clone
 profiles of ``assign_col``, assigns every S-phase cell to its best-correlated clone
 (assign_s_to_clones.py:49-79, vectorised) and runs ``pert_infer_scRT`` on the GPU.
 When ``clone_col`` is None the G1/2 cells are first clustered by KMeans + BIC
-(cncluster.kmeans_cluster, infer_scRT.py:129-138).  The deterministic 'cell' / 'clone' /
-'bulk' levels are outside this build's scope and raise.
+(cncluster.kmeans_cluster, infer_scRT.py:129-138).  ``infer(level='bulk')`` is the
+deterministic baseline (:245-276): the S-phase reads divided by the G1/2 pseudobulk, then the
+threshold binarisation (binarize.py).  The 'cell' and 'clone' levels need statsmodels' lowess
+and ruptures' change-points, which this build cannot check against the reference; they raise.
 """
 from __future__ import annotations
 
 import numpy as np
 import pandas as pd
 
-from . import prep
+from . import prep, rt_profiles
+from .binarize import binarize_profiles, normalize_by_clone
 from .cncluster import kmeans_cluster
 from .pert_model import pert_infer_scRT
 
@@ -187,12 +190,52 @@ class scRT:
         cn_g1_out = pd.DataFrame({})
         if level in ('pyro', 'pert'):
             self.cn_s, supp_s_out_df, cn_g1_out, supp_g1_out_df = self.infer_pert_model()
-        elif level in ('cell', 'clone', 'bulk'):
-            raise NotImplementedError("level='{}' (deterministic non-PERT heuristics) is outside this build's "
-                                      "scope; use level='pert'".format(level))
+        elif level == 'bulk':
+            self.cn_s = self.infer_bulk_level()
+        elif level in ('cell', 'clone'):
+            raise NotImplementedError("level='{}' needs the statsmodels (lowess) and ruptures (change-points) "
+                                      "packages, which this build does not use; level='bulk' is the "
+                                      "deterministic baseline, level='pert' the model".format(level))
         else:
             raise ValueError(level)
         return self.cn_s, supp_s_out_df, cn_g1_out, supp_g1_out_df
+
+    def infer_bulk_level(self):
+        """infer_scRT.py:245-276: every cell in one dummy clone, the G1/2 pseudobulk (median) of
+        ``input_col``, the S-phase cells divided by it into ``rv_col``, then the threshold
+        binarisation.  Sets ``bulk_profile`` and ``manhattan_df``; the caller's tables are not
+        modified (the dummy column lives on copies)."""
+        dummy_clone_col = 'dummy_{}'.format(self.clone_col)
+        cn_g1 = self.cn_g1.assign(**{dummy_clone_col: '1'})
+        cn_s = self.cn_s.assign(**{dummy_clone_col: '1'})
+        self.bulk_profile = consensus_profiles(
+            cn_g1, self.input_col, clone_col=dummy_clone_col, cell_col=self.cell_col, chr_col=self.chr_col,
+            start_col=self.start_col, cn_state_col=None)
+        cn_s = normalize_by_clone(cn_s, self.bulk_profile, input_col=self.input_col, clone_col=dummy_clone_col,
+                                  output_col=self.rv_col, cell_col=self.cell_col, chr_col=self.chr_col,
+                                  start_col=self.start_col, cn_state_col=self.cn_state_col,
+                                  ploidy_col=self.ploidy_col)
+        cn_s, self.manhattan_df = binarize_profiles(
+            cn_s, self.rv_col, rs_col=self.rs_col, frac_rt_col=self.frac_rt_col, thresh_col=self.col5,
+            cell_col=self.cell_col, MEAN_GAP_THRESH=0.7, EARLY_S_SKEW_THRESH=0.2, LATE_S_SKEW_THRESH=-0.2,
+            device=self.engine_kwargs.get("device"))
+        return cn_s.drop(columns=dummy_clone_col)
+
+    def compute_pseudobulk_rt_profiles(self, output_col='pseduobulk', time_col='hours'):
+        """infer_scRT.py:279-282 (the default ``output_col`` is the reference's spelling)."""
+        self.bulk_cn = rt_profiles.compute_pseudobulk_rt_profiles(
+            self.cn_s, self.rv_col, output_col=output_col, time_col=time_col, clone_col=self.clone_col,
+            chr_col=self.chr_col, start_col=self.start_col)
+        return self.bulk_cn
+
+    def calculate_twidth(self, pseudobulk_col='pseudobulk_hours', tfs_col='time_from_scheduled_rt', per_cell=False,
+                         query2=None, curve='sigmoid'):
+        """infer_scRT.py:285-290."""
+        cn = pd.merge(self.cn_s, self.bulk_cn)
+        cn = rt_profiles.compute_time_from_scheduled_column(cn, pseudobulk_col=pseudobulk_col,
+                                                            frac_rt_col=self.frac_rt_col, tfs_col=tfs_col)
+        return rt_profiles.calculate_twidth(cn, tfs_col=tfs_col, rs_col=self.rs_col, cell_col=self.cell_col,
+                                            per_cell=per_cell, query2=query2, curve=curve)
 
     def infer_pert_model(self):
         """infer_scRT.py:127-168."""

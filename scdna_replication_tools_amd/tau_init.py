@@ -168,7 +168,8 @@ def _rng_draws(n: int):
     return first, u
 
 
-def _kmeans_pp(X: torch.Tensor, first: int, u: np.ndarray, fragile: torch.Tensor = None, alts: list = None):
+def _kmeans_pp(X: torch.Tensor, first: int, u: np.ndarray, fragile: torch.Tensor = None, alts: list = None,
+               pp_margin: float = PP_MARGIN):
     """k-means++ for 2 centres, batched over the columns of X (L, N) -> (2, N).  Marks in
     ``fragile`` the columns whose candidate draw or choice is within the rounding margin
     and appends to ``alts`` the (N, 6) second centres the reference could have drawn there
@@ -186,11 +187,11 @@ def _kmeans_pp(X: torch.Tensor, first: int, u: np.ndarray, fragile: torch.Tensor
     best = pots.argmin(0)                                            # first minimum (N,)
     c1 = xc.gather(1, best[:, None])[:, 0]
     if fragile is not None:
-        near = (cums.T.gather(1, cand) - rv.T).abs() <= PP_MARGIN * pot[:, None]
+        near = (cums.T.gather(1, cand) - rv.T).abs() <= pp_margin * pot[:, None]
         prev = cums.T.gather(1, (cand - 1).clamp(min=0))
-        near |= ((prev - rv.T).abs() <= PP_MARGIN * pot[:, None]) & (cand > 0)
+        near |= ((prev - rv.T).abs() <= pp_margin * pot[:, None]) & (cand > 0)
         fragile |= near.any(1)
-        differ = (xc[:, 0] != xc[:, 1]) & ((pots[0] - pots[1]).abs() <= PP_MARGIN * pots.abs().max(0).values)
+        differ = (xc[:, 0] != xc[:, 1]) & ((pots[0] - pots[1]).abs() <= pp_margin * pots.abs().max(0).values)
         fragile |= differ
         if alts is not None:
             nb = torch.cat([(cand - 1).clamp(min=0), cand, (cand + 1).clamp(max=L - 1)], dim=1)   # (N, 6)
@@ -211,10 +212,22 @@ def _assign(X, c, tie_bias: float = 0.0):
     return (d1 - d0 < tie_bias * scale).to(torch.int8)
 
 
+def _near_boundary(X, c, width: float):
+    """Columns with a point within ``width`` (relative, as ``_assign``'s tie) of the label rule's
+    decision."""
+    d1 = c[1] ** 2 - 2 * X * c[1]
+    d0 = c[0] ** 2 - 2 * X * c[0]
+    scale = c[0] ** 2 + c[1] ** 2 + 2 * X.abs() * (c[0].abs() + c[1].abs())
+    return ((d1 - d0).abs() <= width * scale).any(0)
+
+
 def _lloyd(X: torch.Tensor, centers: torch.Tensor, tol: torch.Tensor, max_iter: int = 300,
-           fragile: torch.Tensor = None, tie_bias: float = 0.0):
+           fragile: torch.Tensor = None, tie_bias: float = 0.0, fragile_rel: float = FRAGILE,
+           boundary: float = 0.0):
     """Lloyd's k-means for 2 centres, batched; returns the final labels (L, N) bool
-    (True = centre 1) after sklearn's stopping rule and final re-assignment."""
+    (True = centre 1) after sklearn's stopping rule and final re-assignment.  ``boundary`` > 0
+    also marks in ``fragile`` the columns an assignment of which had a point within that
+    relative width of the decision (the binarisation's single-run form of the tie test)."""
     L, N = X.shape
     labels_old = torch.full((L, N), -1, dtype=torch.int8, device=X.device)
     active = torch.ones(N, dtype=torch.bool, device=X.device)
@@ -233,7 +246,9 @@ def _lloyd(X: torch.Tensor, centers: torch.Tensor, tol: torch.Tensor, max_iter: 
                            torch.where(w1 > 0, s1 / w1.clamp(min=1), c[1])])
         shift = ((new - c) ** 2).sum(0)
         same = (lab == labels_old).all(0)
-        fragile |= active & ~same & ((shift - tol).abs() <= FRAGILE * tol)
+        fragile |= active & ~same & ((shift - tol).abs() <= fragile_rel * tol)
+        if boundary > 0.0:
+            fragile |= active & _near_boundary(X, c, boundary)
         c = torch.where(active[None, :], new, c)
         labels_old = torch.where(active[None, :], lab, labels_old)
         strict |= active & same
@@ -243,12 +258,27 @@ def _lloyd(X: torch.Tensor, centers: torch.Tensor, tol: torch.Tensor, max_iter: 
         if it % SYNC_EVERY == SYNC_EVERY - 1 and not bool(active.any()):
             break
     final = _assign(X, c, tie_bias)
+    if boundary > 0.0:
+        fragile |= ~strict & _near_boundary(X, c, boundary)
     return torch.where(strict[None, :], labels_old, final).bool()
 
 
 def _gmm_means(X: torch.Tensor, lab1: torch.Tensor, max_iter: int = 100, tol: float = 1e-3,
                reg_covar: float = 1e-6, fragile: torch.Tensor = None) -> torch.Tensor:
     """EM of a 2-component 1-D GaussianMixture from the k-means labels; (2, N) means."""
+    return _gmm_fit(X, lab1, max_iter, tol, reg_covar, fragile)[1]
+
+
+def _gmm_log_prob(X: torch.Tensor, w: torch.Tensor, mu: torch.Tensor, var: torch.Tensor) -> torch.Tensor:
+    """Weighted log probabilities (2, L, N) of the E step."""
+    prec = var.rsqrt()
+    y = (X[None] - mu[:, None, :]) * prec[:, None, :]
+    return -0.5 * (float(np.log(2 * np.pi)) + y * y) + torch.log(prec)[:, None, :] + torch.log(w)[:, None, :]
+
+
+def _gmm_fit(X: torch.Tensor, lab1: torch.Tensor, max_iter: int = 100, tol: float = 1e-3,
+             reg_covar: float = 1e-6, fragile: torch.Tensor = None, em_margin: float = EM_MARGIN):
+    """``_gmm_means``' EM with everything it fits: (weights, means, variances), each (2, N)."""
     L, N = X.shape
     eps10 = 10 * torch.finfo(X.dtype).eps
     r1 = lab1.to(X.dtype)
@@ -278,12 +308,12 @@ def _gmm_means(X: torch.Tensor, lab1: torch.Tensor, max_iter: int = 100, tol: fl
         w, mu, var = torch.where(a, w2, w), torch.where(a, mu2, mu), torch.where(a, var2, var)
         change = lb2 - lb
         if fragile is not None:
-            fragile |= active & ((change.abs() - tol).abs() <= EM_MARGIN)
+            fragile |= active & ((change.abs() - tol).abs() <= em_margin)
         lb = torch.where(active, lb2, lb)
         active &= ~(change.abs() < tol)
         if it % SYNC_EVERY == SYNC_EVERY - 1 and not bool(active.any()):
             break
-    return mu
+    return w, mu, var
 
 
 def _percentiles(X: torch.Tensor, qs) -> torch.Tensor:
