@@ -65,10 +65,7 @@ def bin_params(L: int, MEAN_GAP_THRESH=0.7, EARLY_S_SKEW_THRESH=0.2, LATE_S_SKEW
     first, u = tau_init._rng_draws(L)
     p = PertBinParams()
     p.first, p.lloyd_max_iter, p.em_max_iter = first, 300, 100
-    for j, q in enumerate(tau_init.QS):                  # as tau_init._percentiles computes them
-        pos = q * (L - 1)
-        lo = int(np.floor(pos))
-        p.q_lo[j], p.q_hi[j], p.q_t[j] = lo, min(lo + 1, L - 1), pos - lo
+    tau_init.set_percentile_positions(p, L)
     p.u[0], p.u[1] = float(u[0]), float(u[1])
     p.em_tol, p.reg_covar = 1e-3, 1e-6
     p.mean_gap, p.early_skew, p.late_skew = float(MEAN_GAP_THRESH), float(EARLY_S_SKEW_THRESH), float(LATE_S_SKEW_THRESH)

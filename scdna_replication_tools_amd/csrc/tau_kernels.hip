@@ -17,58 +17,11 @@
 // contiguous row per cell; the fp64 standardised values are recomputed from it on each pass
 // instead of being stored, 4 B per bin per pass, L2/MALL resident at genome length).
 
-#include "../../include/pert_hip.h"
-
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
+#include "gmm2_stages.h"
 
 namespace {
 
-constexpr int kT = 256;                 // threads per workgroup
-constexpr int kTW = kT / 64;            // waves per workgroup
-constexpr double kLog2Pi = 1.8378770664093454836;
-constexpr double kEps10 = 10.0 * 2.220446049250313e-16;   // 10 * finfo(float64).eps
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// Fixed-order block sums of NV values; every thread receives the sums.
-template <int NV>
-__device__ __forceinline__ void block_sums(double (&v)[NV], double* sm) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = wave_sum(v[k]);
-  __syncthreads();                      // earlier readers of sm are done
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) sm[k * kTW + w] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    double t = 0.0;
-#pragma unroll
-    for (int ww = 0; ww < kTW; ++ww) t += sm[k * kTW + ww];
-    v[k] = t;
-  }
-}
-
-__device__ __forceinline__ int block_min_i(int v, int* smi) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-  __syncthreads();
-  if (lane == 0) smi[w] = v;
-  __syncthreads();
-  int t = smi[0];
-#pragma unroll
-  for (int ww = 1; ww < kTW; ++ww) t = min(t, smi[ww]);
-  return t;
-}
+using namespace gmm2;
 
 struct Cell {
   const float* x;      // the cell's CN-normalised reads, [L]
@@ -130,80 +83,6 @@ __device__ void lloyd(const Cell& c, double c0, double c1, double tol, double su
   for (int i = threadIdx.x; i < L; i += kT) out[i] = strict ? lab_old[i] : (int8_t)assign2(c.Xc(i), c0, c1, tie);
 }
 
-// Inclusive prefix sums of one 256-element chunk: returns this thread's cumulative value
-// (carry + the chunk's elements up to and including this thread's), *total the carry plus
-// the whole chunk -- both sums in one fixed order.
-__device__ __forceinline__ double chunk_scan(double v, double carry, double* total, double* sm) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const double t = __shfl_up(v, off, 64);
-    if (lane >= off) v += t;
-  }
-  __syncthreads();
-  if (lane == 63) sm[w] = v;
-  __syncthreads();
-  double pre = carry;
-  for (int ww = 0; ww < w; ++ww) pre += sm[ww];
-  double tot = carry;
-#pragma unroll
-  for (int ww = 0; ww < kTW; ++ww) tot += sm[ww];
-  *total = tot;
-  return pre + v;
-}
-
-// Order-preserving map of a double onto uint64 (radix select) and back.
-__device__ __forceinline__ uint64_t okey(double v) {
-  const uint64_t u = (uint64_t)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ikey(uint64_t k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-// Order statistics rank[0..3] (0-based) of the standardised profile by 8-bit radix select,
-// MSB first (8 passes, one 256-bin integer histogram per target in LDS: deterministic).
-__device__ void select4(const Cell& c, const int (&rank)[4], double (&out)[4], uint32_t* hist, uint64_t* s_pref,
-                        long long* s_k) {
-  const int L = c.L;
-  if (threadIdx.x < 4) {
-    s_pref[threadIdx.x] = 0;
-    s_k[threadIdx.x] = rank[threadIdx.x];
-  }
-  for (int pass = 0; pass < 8; ++pass) {
-    const int shift = 56 - 8 * pass;
-    for (int i = threadIdx.x; i < 4 * 256; i += kT) hist[i] = 0;
-    __syncthreads();
-    uint64_t pref[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) pref[j] = s_pref[j];
-    for (int i = threadIdx.x; i < L; i += kT) {
-      const uint64_t key = okey(c.X(i));
-      const uint32_t dig = (uint32_t)(key >> shift) & 255u;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (pass == 0 || (key >> (shift + 8)) == (pref[j] >> (shift + 8))) atomicAdd(&hist[j * 256 + dig], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-      const int j = threadIdx.x;
-      long long cum = 0;
-      for (int d = 0; d < 256; ++d) {
-        const long long h = hist[j * 256 + d];
-        if (cum + h > s_k[j]) {
-          s_pref[j] = pref[j] | ((uint64_t)d << shift);
-          s_k[j] -= cum;
-          break;
-        }
-        cum += h;
-      }
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) out[j] = ikey(s_pref[j]);
-}
-
 // first index i in [0, 100) with th[i] >= v (th ascending), i.e. #{i : th[i] < v}
 __device__ __forceinline__ int count_below(const double* th, double v) {
   int lo = 0, hi = 100;
@@ -225,6 +104,14 @@ __device__ __forceinline__ int count_le(const double* th, double v) {
 
 constexpr double kFix = 4294967296.0;     // 2^32: fixed-point scale of the scan's LDS histograms
 
+// em2's constants, straight from the kernel's parameter struct
+struct EmConsts {
+  const pert_tau_params& p;
+  __device__ __forceinline__ double em_tol() const { return p.em_tol; }
+  __device__ __forceinline__ double em_margin() const { return p.em_margin; }
+  __device__ __forceinline__ double reg_covar() const { return p.reg_covar; }
+};
+
 __global__ __launch_bounds__(kT) void tau_binarize_kernel(int L, int N, const float* __restrict__ norm,
                                                              pert_tau_params p, int8_t* __restrict__ labels,
                                                              int8_t* __restrict__ scratch,
@@ -233,11 +120,9 @@ __global__ __launch_bounds__(kT) void tau_binarize_kernel(int L, int N, const fl
                                                              double* __restrict__ frac_out,
                                                              double* __restrict__ minor_out) {
   __shared__ double sm[8 * kTW];
-  __shared__ double sval[4];
+  __shared__ double sval[2];
   __shared__ int smi[kTW];
-  __shared__ uint32_t s_hist[4 * 256];
-  __shared__ uint64_t s_pref[4];
-  __shared__ long long s_k[4];
+  __shared__ SelectLds s_sel;
   __shared__ double s_th[100];
   __shared__ unsigned long long s_h0[101], s_h1[101];
   __shared__ int s_hn[101], s_e[101];
@@ -252,7 +137,6 @@ __global__ __launch_bounds__(kT) void tau_binarize_kernel(int L, int N, const fl
   Cell c;
   c.x = norm + (size_t)n * L;
   c.L = L;
-  const double invL = 1.0 / (double)L;
 
   // ---- standardisation (X - mean) / std (population std), and the k-means tolerance
   {
@@ -289,69 +173,11 @@ __global__ __launch_bounds__(kT) void tau_binarize_kernel(int L, int N, const fl
     tol = q[0] / (double)L * 1e-4;            // KMeans tolerance: mean variance x 1e-4
   }
 
-  // ---- k-means++ for 2 centres (tau_init._kmeans_pp): first centre from the data-free
-  // RandomState(0) draw, two local trials at u * potential on the cumulative sum
-  const int first = min(max(p.first, 0), L - 1);
-  const double cen0 = c.Xc(first);
-  double pot;
-  {
-    double a[1] = {0.0};
-    for (int i = threadIdx.x; i < L; i += kT) {
-      const double d = c.Xc(i) - cen0;
-      a[0] += d * d;
-    }
-    block_sums<1>(a, sm);
-    pot = a[0];
-  }
-  const double rv[2] = {p.u[0] * pot, p.u[1] * pot};
-  int cand[2] = {-1, -1};
-  double cum_at[2] = {0.0, 0.0}, cum_prev[2] = {0.0, 0.0};
-  {
-    double carry = 0.0;
-    for (int base = 0; base < L && (cand[0] < 0 || cand[1] < 0); base += kT) {
-      const int i = base + threadIdx.x;
-      double v = 0.0;
-      if (i < L) {
-        const double d = c.Xc(i) - cen0;
-        v = d * d;
-      }
-      double total;
-      const double cum = chunk_scan(v, carry, &total, sm);
-      const bool last = base + kT >= L;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        if (cand[t] >= 0) continue;                                   // uniform
-        const int hit = block_min_i((i < L && cum >= rv[t]) ? i : 0x7fffffff, smi);
-        if (hit == 0x7fffffff && !last) continue;                     // uniform
-        const int ci = hit != 0x7fffffff ? hit : L - 1;               // searchsorted, clamped
-        __syncthreads();
-        if (i == ci) sval[0] = cum;
-        if (i == ci - 1) sval[1] = cum;
-        __syncthreads();
-        cand[t] = ci;
-        cum_at[t] = sval[0];
-        cum_prev[t] = ci == base ? carry : sval[1];
-      }
-      carry = total;
-    }
-  }
-  const double xc[2] = {c.Xc(cand[0]), c.Xc(cand[1])};
-  double pots[2] = {0.0, 0.0};
-  for (int i = threadIdx.x; i < L; i += kT) {
-    const double X = c.Xc(i);
-    const double d0 = (X - cen0) * (X - cen0);
-    pots[0] += fmin(d0, (X - xc[0]) * (X - xc[0]));
-    pots[1] += fmin(d0, (X - xc[1]) * (X - xc[1]));
-  }
-  block_sums<2>(pots, sm);
-  const double cen1 = pots[1] < pots[0] ? xc[1] : xc[0];               // first minimum
-  bool frag_pp = false;
-  for (int t = 0; t < 2; ++t) {
-    if (fabs(cum_at[t] - rv[t]) <= p.pp_margin * pot) frag_pp = true;
-    if (cand[t] > 0 && fabs(cum_prev[t] - rv[t]) <= p.pp_margin * pot) frag_pp = true;
-  }
-  if (xc[0] != xc[1] && fabs(pots[0] - pots[1]) <= p.pp_margin * fmax(fabs(pots[0]), fabs(pots[1])))
-    frag_pp = true;
+  // ---- k-means++ for 2 centres (tau_init._kmeans_pp), Lloyd, and where a k-means++ draw sat on a
+  // rounding boundary the alternative Lloyd runs
+  double cen0, cen1;
+  int cand[2];
+  bool frag_pp = kmeans_pp2(c, p, &cen0, &cen1, cand, sm, smi, sval);
 
   bool fragile = false;
   lloyd(c, cen0, cen1, tol, sumXc, tie, p.fragile, p.lloyd_max_iter, lab_old, lab1, &fragile, sm);
@@ -372,113 +198,17 @@ __global__ __launch_bounds__(kT) void tau_binarize_kernel(int L, int N, const fl
     if (same_all) frag_pp = false;
   }
 
-  // ---- EM of the 2-component 1-D mixture from the k-means labels (tau_init._gmm_means;
-  // sklearn fit_predict: at most em_max_iter iterations, |lower-bound change| < em_tol)
-  double w0, w1, mu0, mu1, var0, var1;
-  {
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < L; i += kT) {
-      const double X = c.X(i);
-      const double r1 = (double)lab1[i], r0 = 1.0 - r1;
-      a[0] += r0;
-      a[1] += r1;
-      a[2] += r0 * X;
-      a[3] += r1 * X;
-    }
-    block_sums<4>(a, sm);
-    const double nk0 = a[0] + kEps10, nk1 = a[1] + kEps10;
-    mu0 = a[2] / nk0;
-    mu1 = a[3] / nk1;
-    double q[2] = {0.0, 0.0};
-    for (int i = threadIdx.x; i < L; i += kT) {
-      const double X = c.X(i);
-      const double r1 = (double)lab1[i], r0 = 1.0 - r1;
-      q[0] += r0 * (X - mu0) * (X - mu0);
-      q[1] += r1 * (X - mu1) * (X - mu1);
-    }
-    block_sums<2>(q, sm);
-    var0 = q[0] / nk0 + p.reg_covar;
-    var1 = q[1] / nk1 + p.reg_covar;
-    w0 = nk0 * invL;
-    w1 = nk1 * invL;
-    const double ws = w0 + w1;
-    w0 /= ws;
-    w1 /= ws;
-  }
-  double lb = -INFINITY;
-  for (int it = 0; it < p.em_max_iter; ++it) {
-    const double pr0 = 1.0 / sqrt(var0), pr1 = 1.0 / sqrt(var1);
-    const double lp0 = log(pr0), lp1 = log(pr1), lw0 = log(w0), lw1 = log(w1);
-    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < L; i += kT) {
-      const double X = c.X(i);
-      const double y0 = (X - mu0) * pr0, y1 = (X - mu1) * pr1;
-      const double l0 = (-0.5 * (kLog2Pi + y0 * y0) + lp0) + lw0, l1 = (-0.5 * (kLog2Pi + y1 * y1) + lp1) + lw1;
-      const double m = fmax(l0, l1);
-      const double lpn = m + log(exp(l0 - m) + exp(l1 - m));
-      const double r0 = exp(l0 - lpn), r1 = exp(l1 - lpn);
-      a[0] += r0;
-      a[1] += r1;
-      a[2] += r0 * X;
-      a[3] += r1 * X;
-      a[4] += lpn;
-    }
-    block_sums<5>(a, sm);
-    const double nk0 = a[0] + kEps10, nk1 = a[1] + kEps10;
-    const double m0 = a[2] / nk0, m1 = a[3] / nk1;
-    double q[2] = {0.0, 0.0};
-    for (int i = threadIdx.x; i < L; i += kT) {
-      const double X = c.X(i);
-      const double y0 = (X - mu0) * pr0, y1 = (X - mu1) * pr1;
-      const double l0 = (-0.5 * (kLog2Pi + y0 * y0) + lp0) + lw0, l1 = (-0.5 * (kLog2Pi + y1 * y1) + lp1) + lw1;
-      const double m = fmax(l0, l1);
-      const double lpn = m + log(exp(l0 - m) + exp(l1 - m));
-      const double r0 = exp(l0 - lpn), r1 = exp(l1 - lpn);
-      q[0] += r0 * (X - m0) * (X - m0);
-      q[1] += r1 * (X - m1) * (X - m1);
-    }
-    block_sums<2>(q, sm);
-    double nw0 = nk0 * invL, nw1 = nk1 * invL;
-    const double ws = nw0 + nw1;
-    w0 = nw0 / ws;
-    w1 = nw1 / ws;
-    mu0 = m0;
-    mu1 = m1;
-    var0 = q[0] / nk0 + p.reg_covar;
-    var1 = q[1] / nk1 + p.reg_covar;
-    const double lb2 = a[4] * invL;
-    const double change = lb2 - lb;
-    lb = lb2;
-    if (fabs(fabs(change) - p.em_tol) <= p.em_margin) fragile = true;
-    if (fabs(change) < p.em_tol) break;
-  }
+  // ---- EM of the 2-component 1-D mixture from the k-means labels (tau_init._gmm_means)
+  Mix fit;
+  em2(c, lab1, p.em_max_iter, EmConsts{p}, &fit, &fragile, true, sm);
+  const double mu0 = fit.mu0, mu1 = fit.mu1;
+
   // ---- levels (pert_model.py:377-400; tau_init._levels_scan): the GMM means, or percentiles of
   // the profile chosen by its skew when the means are closer than MEAN_GAP_THRESH
-  double b0 = fmin(mu0, mu1), b1 = fmax(mu0, mu1);
-  const double gap = fabs(mu0 - mu1);
-  if (fabs(gap - p.mean_gap) <= p.fragile_abs) fragile = true;
-  if (gap < p.mean_gap) {
-    double m[2] = {0.0, 0.0};
-    for (int i = threadIdx.x; i < L; i += kT) {
-      const double xc = c.Xc(i);
-      m[0] += xc * xc;
-      m[1] += xc * xc * xc;
-    }
-    block_sums<2>(m, sm);
-    const double m2 = m[0] / (double)L, m3 = m[1] / (double)L;
-    const double sk = m3 / pow(m2, 1.5);
-    if (fabs(sk - p.early_skew) <= p.fragile_abs || fabs(sk - p.late_skew) <= p.fragile_abs) fragile = true;
-    const bool early = sk > p.early_skew, late = !early && sk < p.late_skew;
-    const int qa = early ? 2 : (late ? 0 : 1), qb = early ? 4 : (late ? 2 : 3);   // (50, 95) / (5, 50) / (25, 75)
-    const int rank[4] = {p.q_lo[qa], p.q_hi[qa], p.q_lo[qb], p.q_hi[qb]};
-    double v[4];
-    select4(c, rank, v, s_hist, s_pref, s_k);
-    // np.percentile 'linear' with numpy's two-sided lerp (tau_init._percentiles)
-    const double ta = p.q_t[qa], tb = p.q_t[qb];
-    const double da = v[1] - v[0], dbq = v[3] - v[2];
-    b0 = ta >= 0.5 ? v[1] - da * (1.0 - ta) : v[0] + da * ta;
-    b1 = tb >= 0.5 ? v[3] - dbq * (1.0 - tb) : v[2] + dbq * tb;
-  }
+  double b0, b1;
+  if (levels2(c, p, mu0, mu1, LevelTests{p.mean_gap, p.fragile_abs, p.early_skew, p.late_skew, p.fragile_abs}, &b0,
+              &b1, sm, &s_sel))
+    fragile = true;
 
   // ---- the 100-threshold scan (:402-423) with the rounding margins of tau_init._levels_scan.
   // Threshold i binarises x to b1 iff x > th[i]; with c(x) = #{i : th[i] < x} the distance
@@ -575,11 +305,8 @@ extern "C" int pert_tau_binarize(int32_t L, int32_t N, const float* norm, const 
                                  int8_t* labels, int8_t* scratch, double* means, int32_t* flags, double* frac,
                                  double* minor, hipStream_t stream) {
   if (L < 2 || N < 1 || !norm || !p || !labels || !scratch || !means || !flags || !frac || !minor) return PERT_E_ARG;
-  if (p->first < 0 || p->first >= L || p->lloyd_max_iter < 1 || p->em_max_iter < 1) return PERT_E_ARG;
-  for (int j = 0; j < 5; ++j)
-    if (p->q_lo[j] < 0 || p->q_lo[j] >= L || p->q_hi[j] < 0 || p->q_hi[j] >= L) return PERT_E_ARG;
-  hipLaunchKernelGGL(tau_binarize_kernel, dim3(N, 2), dim3(kT), 0, stream, L, N, norm, *p, labels, scratch,
+  if (!gmm2::params_ok(L, *p)) return PERT_E_ARG;
+  hipLaunchKernelGGL(tau_binarize_kernel, dim3(N, 2), dim3(gmm2::kT), 0, stream, L, N, norm, *p, labels, scratch,
                      means, flags, frac, minor);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PERT_OK : PERT_E_HIP_BASE + (int)e;
+  return gmm2::launch_status();
 }

@@ -407,6 +407,15 @@ def _kmeans_em(X: torch.Tensor, Xc: torch.Tensor, tie_bias: float):
 QS = (0.05, 0.25, 0.5, 0.75, 0.95)          # the percentiles the levels may take (pert_model.py:388-399)
 
 
+def set_percentile_positions(p, L: int):
+    """Fill q_lo / q_hi / q_t of a pert_tau_params or pert_bin_params: the two order statistics
+    and the lerp weight of np.percentile 'linear' at each of QS, as _percentiles computes them."""
+    for j, q in enumerate(QS):
+        pos = q * (L - 1)
+        lo = int(np.floor(pos))
+        p.q_lo[j], p.q_hi[j], p.q_t[j] = lo, min(lo + 1, L - 1), pos - lo
+
+
 def tau_params(L: int):
     """The pert_tau_params of the batched pass at L bins (the constants of this module and the
     sklearn / numpy defaults the reference runs)."""
@@ -414,10 +423,7 @@ def tau_params(L: int):
     first, u = _rng_draws(L)
     p = PertTauParams()
     p.first, p.lloyd_max_iter, p.em_max_iter = first, 300, 100
-    for j, q in enumerate(QS):                       # as _percentiles computes them
-        pos = q * (L - 1)
-        lo = int(np.floor(pos))
-        p.q_lo[j], p.q_hi[j], p.q_t[j] = lo, min(lo + 1, L - 1), pos - lo
+    set_percentile_positions(p, L)
     p.u[0], p.u[1] = float(u[0]), float(u[1])
     p.tie, p.pp_margin, p.fragile, p.em_margin = TIE, PP_MARGIN, FRAGILE, EM_MARGIN
     p.em_tol, p.reg_covar = 1e-3, 1e-6

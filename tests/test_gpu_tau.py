@@ -1,6 +1,6 @@
-"""GPU: the tau initialiser's k-means / EM stage as one HIP launch (pert_tau_kmeans_em,
-csrc/tau_kernels.hip) against the tensor program it replaces (tau_init._kmeans_em, the same
-algorithm as ~20 launches per iteration), and the product entry point on the GPU
+"""GPU: the tau initialiser's batched pass as one HIP launch (pert_tau_binarize,
+csrc/tau_kernels.hip) against the tensor programs it replaces (tau_init._kmeans_em and
+_levels_scan, the same algorithm as ~20 launches per iteration), and the product entry point on the GPU
 (guess_times_batched on cuda: kernel + levels / scan + exact host path for the flagged
 cells) against the per-cell sklearn restatement of the reference (prep.guess_times,
 pert_model.py:364-457) for every cell."""
@@ -83,6 +83,17 @@ def test_kernel_matches_tensor_program(L, n_s, n_g, seed, reads_per_bin):
     print("cells with percentile levels:", close // 2, "of", norm.shape[1])
     if reads_per_bin == "mixture":
         assert close // 2 >= 20
+
+
+def test_two_launches_are_bit_identical():
+    """Every reduction of the batched pass is a fixed-order block sum: a second launch on the same
+    input returns the same bytes, both tie directions."""
+    reads, states = _profiles(150, 50, 271, 1)
+    norm = _norm(reads, states).cuda()
+    a, b = tau_init.binarize_native(norm), tau_init.binarize_native(norm)
+    for r in range(2):
+        for k in ("labels", "mu", "fragile", "pp", "scan", "frac", "minor"):
+            assert a[r][k].cpu().numpy().tobytes() == b[r][k].cpu().numpy().tobytes(), (r, k)
 
 
 def test_guess_times_percentile_levels_match_reference_every_cell():
