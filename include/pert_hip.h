@@ -339,6 +339,28 @@ int pert_svi_run_sharded(const pert_problem* prob, pert_state* st, const pert_ad
  * left bit-identical.  Steps 2/3 shards only. */
 int pert_stream_ceiling(const pert_problem* prob, pert_state* st, hipStream_t stream);
 
+/* Posterior marginals of the enumerated latent states at the current parameters (steps 2/3;
+ * one pass after a fit, post_kernels.hip).  For every (bin, cell) the posterior over the 2P
+ * joint states is gamma(c, r) = softmax_{c,r} s(c, r), s the joint score the passes enumerate
+ * (log pi~_c + log Bern(r | phi) + NB'(c (1 + r)); the Dirichlet prior does not enter given pi).
+ * Read only: prob->reads [L][ldn], gcf, lamb / log1m_lam, rho_fixed / a_fixed (step 3);
+ * st->params with st->lay, st->z_pi in its wave tiles [ldn/64][L][P][64]; st->bins_per_tile
+ * (0 = default) sets the bins per wave.  Nothing in st is written.
+ *   rep_prob  float [L][ldn]     P(rep = 1) = sum_c gamma(c, 1)                     (required)
+ *   cn_state  uint8 [L][ldn]     a CN state per element, e.g. st->cn_out after a decode
+ *   cn_prob   float [L][ldn]     the cn marginal gamma(k, 0) + gamma(k, 1) at k = cn_state: the
+ *                                probability of the call the caller holds (0 for a state >= P);
+ *                                cn_state and cn_prob are given together or both NULL
+ *   cn_marg   float [P][L][ldn]  all P cn marginals                                 (or NULL)
+ * Columns n >= N of the outputs are left untouched.  No atomics and no cross-lane sums: reruns
+ * are bit-identical.  PERT_E_ARG for a null prob, st or rep_prob, a step-1 problem, cn_prob without
+ * cn_state (or the reverse), L < 1, N < 1, ldn < N or ldn not a multiple of PERT_BLOCK; then
+ * PERT_E_UNSUPPORTED_P / PERT_E_UNSUPPORTED_K for P outside [PERT_MIN_P, PERT_MAX_P] / K1 outside
+ * [1, PERT_MAX_K1]; then PERT_E_ARG for a null reads, gcf, st->params or st->z_pi, a null rho_fixed
+ * in step 3, or more than 65535 bin tiles (ceil(L / bins_per_tile)); all before any launch. */
+int pert_enum_posterior(const pert_problem* prob, const pert_state* st, const uint8_t* cn_state,
+                        float* rep_prob, float* cn_prob, float* cn_marg, hipStream_t stream);
+
 /* tau initialiser (guess_times, pert_model.py:426-457): the batched pass of
  * manhattan_binarization (:364-423) for every cell in ONE launch, in fp64 -- standardisation,
  * GaussianMixture(n_components=2, random_state=0) (k-means++ and Lloyd initialisation, then EM),
@@ -542,6 +564,10 @@ int pert_selftest_enum_cellbin_host(int32_t P, int64_t n, const float* x, const 
 int pert_selftest_enum_online_host(int32_t P, int64_t n, const float* x, const float* em1,
                                    const float* S1, const float* z, float log1m_lam, const float* D,
                                    const float* phi, float* E, float* gz);
+/* pert_enum_posterior's per-element arithmetic (pert_math.h enum_posterior) on the host:
+ * x, D, phi float [n], z float [n][P] -> p_rep float [n], p_cn float [n][P]. */
+int pert_selftest_enum_posterior_host(int32_t P, int64_t n, const float* x, const float* z, float log1m_lam,
+                                      const float* D, const float* phi, float* p_rep, float* p_cn /* [n][P] */);
 
 const char* pert_version(void);
 

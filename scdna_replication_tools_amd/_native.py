@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "pert_comm_inject_fault", "pert_finalize_shared", "pert_finalize_cells", "pert_comm_set_options",
     "pert_comm_overlap", "pert_comm_allreduce_async", "pert_comm_join", "pert_rt_counts", "pert_rt_tfs_hist",
     "pert_sim_raw", "pert_sim_cells", "pert_sim_reads", "pert_sim_normalise", "pert_rt_binarize",
+    "pert_enum_posterior", "pert_selftest_enum_posterior_host",
 )
 
 # include/pert_hip.h status codes of a sharded fit's communicator
@@ -228,6 +229,9 @@ def load(path: str, gil: bool = True):
     handle.pert_selftest_enum_cellbin_host.argtypes = [i32, i64, fp, fp, fp, fp, c_float, fp, fp, fp, fp,
                                                        fp, fp, fp, POINTER(i32)]
     handle.pert_selftest_enum_online_host.argtypes = [i32, i64, fp, fp, fp, fp, c_float, fp, fp, fp, fp]
+    handle.pert_enum_posterior.argtypes = [POINTER(PertProblem), POINTER(PertState), c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]
+    handle.pert_selftest_enum_posterior_host.argtypes = [i32, i64, fp, fp, c_float, fp, fp, fp, fp]
     handle.pert_tau_binarize.argtypes = [i32, i32, c_void_p, POINTER(PertTauParams), c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_binarize.argtypes = [i32, i32, c_void_p, POINTER(PertBinParams), c_void_p, c_void_p, c_void_p,
@@ -333,3 +337,18 @@ def selftest_enum_online_host(P, x, em1, S1, z, log1m_lam, D, phi):
                                                _fptr(D), _fptr(phi), _fptr(E), _fptr(gz)),
           "pert_selftest_enum_online_host")
     return dict(E=E, gz=gz)
+
+
+def selftest_enum_posterior_host(P, x, z, log1m_lam, D, phi):
+    """Host evaluation of pert_math.h enum_posterior (test-only): P(rep = 1) [n] and the cn
+    marginals [n][P] of each element's 2P joint states."""
+    import numpy as np
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    x, z, D, phi = map(f, (x, z, D, phi))
+    n = x.size
+    p_rep = np.empty(n, np.float32)
+    p_cn = np.empty((n, P), np.float32)
+    check(lib().pert_selftest_enum_posterior_host(P, n, _fptr(x), _fptr(z), float(log1m_lam), _fptr(D), _fptr(phi),
+                                                  _fptr(p_rep), _fptr(p_cn)),
+          "pert_selftest_enum_posterior_host")
+    return dict(p_rep=p_rep, p_cn=p_cn)

@@ -1011,4 +1011,105 @@ PERT_HD float clipped_sigmoid(float zz, float* dmask) {
   return s;
 }
 
+// ----------------------------------------------------------------- posterior of one cell.bin
+// The posterior over the 2P joint states of one (bin, cell) at fixed parameters (post_kernels.hip):
+// gamma(c, r) = softmax_{c,r} s(c, r), returned as its marginals
+//   p_rep = sum_c gamma(c, 1)   (the return value)   and   p_cn[k] = gamma(k, 0) + gamma(k, 1),
+// UNMASKED -- EnumFwd::gcm / gt carry the clamp masks of the gradient and are not these.  The
+// Dirichlet prior does not enter: given pi the discrete posterior has no eta term.
+// The scores are built exactly as enum_forward builds them (clamped log pi~, clamped
+// Bernoulli(phi), the NB term per distinct chi with the asymptotic branch for D >= kAsymMin and
+// the delta < 1 clamp otherwise): those ~50 lines are DUPLICATED here on purpose, so that
+// enum_forward / enum_online and the code objects of the step and decode kernels stay exactly
+// as they are; folding both into one shared score builder is a later clean-up.
+// se is summed per cn state (e(k, 0) + e(k, 1), then over k), so sum_k p_cn[k] = 1 within
+// (P + 2) eps32; both outputs are kept in [0, 1] (the reciprocal is good to an ulp only).
+template <int P>
+PERT_HD float enum_posterior(float x, float invx, const float (&z)[P], float log1m_lam, float D, float phi_raw,
+                             float (&p_cn)[P]) {
+  // Bernoulli(phi) with the in-place clamps of pert_model.py:622-623
+  const float phic = fmed3(phi_raw, 0.001f, 0.999f);
+  const float lphi = flog(phic);
+  const float l1mphi = flog(1.0f - phic);
+
+  // pi = softmax(z) and log(clamp_probs(pi)), as enum_forward
+  float m = z[0];
+  int jmax = 0;
+#pragma unroll
+  for (int k = 1; k < P; ++k) { if (z[k] > m) { m = z[k]; jmax = k; } }
+  float e[P];
+  float t = 0.0f;
+#pragma unroll
+  for (int k = 0; k < P; ++k) {
+    e[k] = (k == jmax) ? 1.0f : fexp(z[k] - m);
+    t += (k == jmax) ? 0.0f : e[k];
+  }
+  const float inv1t = frcp(1.0f + t);
+  const float lse1p = log1p_corr(t, inv1t);
+  float s[2 * P];
+#pragma unroll
+  for (int k = 0; k < P; ++k) {
+    const float pk = e[k] * inv1t;
+    const float om = (k == jmax) ? t * inv1t : 1.0f - pk;
+    const bool hi = om < kEps32;
+    const bool lo = pk < kEps32;
+    const float lc = hi ? kLog1mEps32 : (lo ? kLogEps32 : (z[k] - m) - lse1p);
+    s[k] = lc + l1mphi;
+    s[P + k] = lc + lphi;
+  }
+
+  // negative-binomial part per distinct chi, folded straight into the scores
+  const float n_clamped = log1m_lam + lambda_delta1(x, invx);   // delta == 1 (chi == 0 or chi D < 1)
+  s[0] += n_clamped;
+  s[P] += n_clamped;
+  if (D >= kAsymMin) {
+    const float rD = frcp(D);
+    const float ldx = x > 0.0f ? flog(D) - flog(x) : 0.0f;
+#pragma unroll
+    for (int chi = 1; chi < 2 * P - 1; ++chi) {
+      if (!chi_needed<P>(chi)) continue;
+      const float d = (float)chi * D;
+      float lam, psi;
+      nb_lgdiff_asym_hoisted(d, rD * (1.0f / (float)chi), x, ldx + kLogInt[chi], lam, psi);
+      const float nchi = d * log1m_lam + lam;
+      if (chi < P) s[chi] += nchi;
+      if ((chi % 2) == 0) s[P + chi / 2] += nchi;
+    }
+  } else {
+#pragma unroll
+    for (int chi = 1; chi < 2 * P - 1; ++chi) {
+      if (!chi_needed<P>(chi)) continue;
+      const float d = (float)chi * D;
+      float nchi;
+      if (d < 1.0f) {
+        nchi = n_clamped;
+      } else {
+        float lam, psi;
+        nb_lgdiff(d, x, invx, lam, psi);
+        nchi = d * log1m_lam + lam;
+      }
+      if (chi < P) s[chi] += nchi;
+      if ((chi % 2) == 0) s[P + chi / 2] += nchi;
+    }
+  }
+
+  // gamma = softmax of the 2P scores; the marginals
+  float smax = s[0];
+#pragma unroll
+  for (int i = 1; i < 2 * P; ++i) smax = fmaxf(smax, s[i]);
+  float se = 0.0f, g1 = 0.0f;
+#pragma unroll
+  for (int c = 0; c < P; ++c) {
+    const float e1 = fexp(s[P + c] - smax);
+    const float ec = fexp(s[c] - smax) + e1;
+    p_cn[c] = ec;
+    se += ec;
+    g1 += e1;
+  }
+  const float inv_se = frcp(se);
+#pragma unroll
+  for (int c = 0; c < P; ++c) p_cn[c] = fminf(p_cn[c] * inv_se, 1.0f);
+  return fminf(g1 * inv_se, 1.0f);
+}
+
 }  // namespace pert

@@ -679,6 +679,7 @@ class PertShard:
             self.v_pi = torch.zeros_like(self.z_pi)
         self.cn_out = torch.zeros((L, ldn), dtype=torch.uint8, device=dev)
         self.rep_out = torch.zeros((L, ldn), dtype=torch.uint8, device=dev)
+        self.rep_prob = self.cn_prob = self.cn_marg = None     # posterior()'s outputs, allocated on first use
 
         self.pass_events = None      # list -> (start, end) HIP events around every pass
         self.pass_event_stride = 1   # (one-rank loop) events around every stride-th iteration's pass
@@ -1262,3 +1263,29 @@ class PertShard:
             raise ValueError("step 1 has no latent discrete sites")
         self._pass(nat.MODE_DECODE)
         return self.cn_out[:, :self.N], self.rep_out[:, :self.N]
+
+    def posterior(self, cn_marginal: bool = False):
+        """Posterior marginals of the enumerated states at the current parameters
+        (pert_enum_posterior): ``rep_prob`` = P(rep = 1) and ``cn_prob`` = the probability of
+        the decoded CN state, (L, N) float32 each, and with ``cn_marginal`` all P CN marginals
+        ``cn_marg`` (P, L, N).  Runs ``decode()`` first, so ``cn_out`` / ``rep_out`` are the
+        calls these probabilities belong to.  Device tensors, used in place like ``decode()``'s:
+        the next call overwrites them."""
+        if self.kind == nat.KIND_STEP1:
+            raise ValueError("step 1 has no latent discrete sites")
+        self.decode()
+        L, N, ldn = self.L, self.N, self.ldn
+        if self.rep_prob is None:
+            self.rep_prob = torch.zeros((L, ldn), dtype=torch.float32, device=self.device)
+            self.cn_prob = torch.zeros((L, ldn), dtype=torch.float32, device=self.device)
+        if cn_marginal and self.cn_marg is None:
+            self.cn_marg = torch.zeros((self.P, L, ldn), dtype=torch.float32, device=self.device)
+        marg = self.cn_marg if cn_marginal else None
+        with self._dev():
+            nat.check(self.lib.pert_enum_posterior(ctypes.byref(self._prob), ctypes.byref(self._state),
+                                                   _ptr(self.cn_out), _ptr(self.rep_prob), _ptr(self.cn_prob),
+                                                   _ptr(marg), self._stream()), "pert_enum_posterior")
+        out = {"rep_prob": self.rep_prob[:, :N], "cn_prob": self.cn_prob[:, :N]}
+        if cn_marginal:
+            out["cn_marg"] = self.cn_marg[:, :, :N]
+        return out

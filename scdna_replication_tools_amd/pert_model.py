@@ -85,10 +85,15 @@ def _np(v):
     return np.asarray(v)
 
 
+# optional MapTrace nodes (posterior=True) and the output columns package_s_output makes of them
+_POSTERIOR_COLUMNS = (("rep_prob", "model_rep_prob"), ("cn_prob", "model_cn_prob"))
+
+
 class MapTrace:
     """The part of a Pyro trace that ``package_s_output`` reads (``trace.nodes[name]['value']``),
     for the MAP values of one fit: expose_u / expose_rho / expose_a / expose_tau and the
-    decoded ``cn`` / ``rep`` (pert_model.py:472-477)."""
+    decoded ``cn`` / ``rep`` (pert_model.py:472-477); optionally ``rep_prob`` / ``cn_prob``, the
+    posterior probabilities of replication and of the decoded CN state (loci x cells)."""
 
     def __init__(self, **values):
         self.nodes = {k: {"value": v} for k, v in values.items()}
@@ -174,7 +179,7 @@ class pert_infer_scRT():
                  max_iter_step1=None, min_iter_step1=None, max_iter_step3=None, min_iter_step3=None,
                  cuda=False, seed=0, P=13, K=4, J=5, upsilon=6, run_step3=True, *, device=None,
                  init_method='sampled', dirichlet_mode='torch32', n_jobs=1, tau_init_method='batched',
-                 process_group=None, log_steps=True):
+                 process_group=None, log_steps=True, posterior=False):
         self.cn_s = cn_s
         self.cn_g1 = cn_g1
         self.input_col = input_col
@@ -222,6 +227,10 @@ class pert_infer_scRT():
         self.tau_threads = n_jobs if n_jobs > 1 else default_threads()
         self.tau_init_method = tau_init_method
         self.log_steps = log_steps
+        # also report the posterior probabilities the MAP calls are made from: float32 columns
+        # model_rep_prob = P(rep = 1) and model_cn_prob = P(cn = model_cn_state) (no reference
+        # counterpart; PertShard.posterior)
+        self.posterior = bool(posterior)
         self.timings = {}
         self.iters = {}
         self.launched = {}
@@ -479,12 +488,19 @@ class pert_infer_scRT():
                          is_root=dd.rank == 0, n_cells_total=2 * NG, allreduce=dd.allreduce, comm=dd.comm)
 
     def _decode(self, shard: PertShard, dd: _Dist):
+        """The MAP states and constrained sites of a fit, gathered over the ranks; with
+        ``posterior=True`` the dict also carries ``rep_prob`` / ``cn_prob`` (loci x cells)."""
         cn, rep = shard.decode()
+        # (posterior() decodes again itself: the same states, one more millisecond-scale launch)
+        post = shard.posterior() if self.posterior else None
         c = shard.constrained()
         cn = dd.gather_cells(cn.cpu().numpy())
         rep = dd.gather_cells(rep.cpu().numpy())
         for k in ("expose_tau", "expose_u"):
             c[k] = dd.gather_cells(np.asarray(c[k]))
+        if post is not None:
+            for k in ("rep_prob", "cn_prob"):
+                c[k] = dd.gather_cells(post[k].cpu().numpy())
         return cn, rep, c
 
     def run_pert_model(self):
@@ -613,7 +629,8 @@ class pert_infer_scRT():
             tic = time.perf_counter()
             cn_map, rep_map, c2 = self._decode(s2, dd)
             trace_s = MapTrace(cn=cn_map, rep=rep_map, expose_u=c2["expose_u"], expose_rho=c2["expose_rho"],
-                               expose_a=c2["expose_a"], expose_tau=c2["expose_tau"])
+                               expose_a=c2["expose_a"], expose_tau=c2["expose_tau"],
+                               **{k: c2[k] for k in ("rep_prob", "cn_prob") if k in c2})
             cn_s_out, supp_s_out_df = self.package_s_output(
                 self.cn_s, trace_s, self._axes(inp.cells_s, inp.keys_s), lambda_fit, losses_g, losses_s)
             self.timings["decode_package_s"] = time.perf_counter() - tic
@@ -644,7 +661,8 @@ class pert_infer_scRT():
                 tic = time.perf_counter()
                 cn3, rep3, c3 = self._decode(s3, dd)
                 trace_s2 = MapTrace(cn=cn3, rep=rep3, expose_u=c3["expose_u"], expose_rho=rho_fit, expose_a=a_fit,
-                                    expose_tau=c3["expose_tau"])
+                                    expose_tau=c3["expose_tau"],
+                                    **{k: c3[k] for k in ("rep_prob", "cn_prob") if k in c3})
                 cn_g1_out, supp_g1_out_df = self.package_s_output(
                     self.cn_g1, trace_s2, self._axes(inp.cells_g, inp.keys_g), lambda_fit, losses_g, losses_s2)
                 self.timings["decode_package_g"] = time.perf_counter() - tic
@@ -686,7 +704,9 @@ class pert_infer_scRT():
         model_tau / model_u, per bin model_rho -- the rows, row order and dtypes of the
         reference's melt + inner merges on (cell, chr, start) -- plus the supp frame of
         lambda, a and the loss traces.  ``trace_s``: a MapTrace (or anything with
-        ``nodes[name]['value']``); ``cn_s_reads_df``: the (loci x cells) frame or a PivotAxes."""
+        ``nodes[name]['value']``); ``cn_s_reads_df``: the (loci x cells) frame or a PivotAxes.
+        A trace that carries the nodes ``rep_prob`` / ``cn_prob`` (loci x cells, ``posterior=True``)
+        adds the float32 columns model_rep_prob / model_cn_prob after the reference's."""
         nodes = trace_s.nodes
         v = lambda k: _np(nodes[k]["value"])
         cells = np.asarray(cn_s_reads_df.columns)
@@ -718,6 +738,9 @@ class pert_infer_scRT():
                 'model_u': np.repeat(per_cell("expose_u"), L),
                 'model_rho': np.tile(per_cell("expose_rho"), len(cells)),
             }
+            for node, name in _POSTERIOR_COLUMNS:
+                if node in nodes:
+                    model[name] = prep.transpose_cast(v(node), np.float32).reshape(-1)
         else:
             keep = (ci >= 0) & (li >= 0)
             base = cn_s.loc[keep] if not keep.all() else cn_s
@@ -729,6 +752,9 @@ class pert_infer_scRT():
                 'model_u': per_cell("expose_u")[ci],
                 'model_rho': per_cell("expose_rho")[li],
             }
+            for node, name in _POSTERIOR_COLUMNS:
+                if node in nodes:
+                    model[name] = v(node)[li, ci].astype(np.float32)
         # new columns side by side with the (sorted) input rows, without copying its blocks:
         # each inserted column is a block of its own (reset_index(drop=True) would deep-copy
         # the whole long table, and a concat consolidates every block of one dtype)
