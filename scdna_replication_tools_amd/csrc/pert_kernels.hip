@@ -155,11 +155,6 @@ __device__ __forceinline__ void dma_run(const void* gsrc, float* ldst, int lane)
 template <int BYTES>
 constexpr int dma_count() { return BYTES / 1024 + (BYTES % 1024) / 256 + ((BYTES % 256) == 128 ? 1 : 0); }
 
-// the DMA pass's per-(bin, cell) arithmetic: 1 = enum_online + the packed tail (as enum3_kernel),
-// 0 = enum_forward + the scalar tail (A/B knob)
-#ifndef PERT_V0_ONLINE
-#define PERT_V0_ONLINE 1
-#endif
 #ifndef PERT_ENUM3_GROUP
 #define PERT_ENUM3_GROUP 6
 #endif
@@ -316,13 +311,8 @@ __global__ void __launch_bounds__(64, 2) enum_dma_kernel(pert_problem pr, pert_s
     const float D = ucc * omega;                           // :636-640 (delta = chi D)
     const float t = tau - rho;                             // :616
     const float phi = frcp(1.0f + fexp(-a_val * t));       // :619
-#if PERT_V0_ONLINE
     EnumOnline<P> o;
     enum_online<P, kEnum3Group, !kDecode, kDecode>(x, invx, z, pr.log1m_lam, D, phi, o);
-#else
-    EnumFwd<P> o;
-    enum_forward<P, !kDecode, kDecode>(x, invx, z, pr.log1m_lam, D, phi, o);
-#endif
     float gtv = 0.0f;
     if (kDecode) {
       st.cn_out[(size_t)l * ldn + n] = (uint8_t)(o.argmax % P);
@@ -350,7 +340,6 @@ __global__ void __launch_bounds__(64, 2) enum_dma_kernel(pert_problem pr, pert_s
         S1 = row[P];
         Arow = row[P + 1];
       }
-#if PERT_V0_ONLINE
       // the gradient and Adam of the logits in plane pairs, packed fp32 (as enum3_kernel)
       const float S1s = S1 + o.sgm;
       int jmax;
@@ -410,39 +399,6 @@ __global__ void __launch_bounds__(64, 2) enum_dma_kernel(pert_problem pr, pert_s
 #pragma unroll
         for (int k = 0; k < K1T; ++k) acc[k] += ge * g[k];
       }
-#else
-      float gz[P];
-      const float dirv = dir_site_round(enum_tail<P>(o, zt, em1, S1, gz), Arow);
-      if (valid) {
-        loss += o.E + dirv;
-        gtv = o.gt;
-        accT += a_val * o.gt;
-        ga += t * o.gt;
-        const float ge = o.gD * omega;
-#pragma unroll
-        for (int k = 0; k < K1T; ++k) acc[k] += ge * g[k];
-      }
-      if (kStep) {
-        const float* mb = lds + 2 * SF;
-        float* zo = st.z_pi + tile + lane;
-        float* mo = st.m_pi + tile + lane;
-        float* vo = st.v_pi + tile + lane;
-#pragma unroll
-        for (int k = 0; k < P; ++k) {
-          const float gl = -gz[k];                          // d(-ELBO)/dz
-          const float m1 = hp.beta1 * mb[k * 64 + lane] + (1.0f - hp.beta1) * gl;
-          const float v1 = hp.beta2 * mb[ZF + k * 64 + lane] + (1.0f - hp.beta2) * gl * gl;
-          const float denom = __builtin_sqrtf(v1) * hp.inv_bc2_sqrt + hp.eps;
-          store_stream(zo + k * 64, zt[k] - hp.step_size * m1 * frcp(denom));
-          store_stream(mo + k * 64, m1);
-          store_stream(vo + k * 64, v1);
-        }
-      } else {
-        float* gp = st.g_pi + tile + lane;
-#pragma unroll
-        for (int k = 0; k < P; ++k) gp[k * 64] = -gz[k];
-      }
-#endif
     }
     if (!kDecode && !frozen) {
       const float ws = wave_sum(gtv);

@@ -371,14 +371,36 @@ PERT_HD float jmax_grad(int jmax, const float (&em)[P + 1], const float* gcm, fl
   return ((S1 - wj) + (sgm - gj)) - (S1 + sgm) * om;
 }
 
-template <int P, bool WANT_GRAD, bool WANT_ARGMAX>
-PERT_HD void enum_forward(float x, float invx, const float (&z)[P], float log1m_lam, float D,
-                          float phi_raw, EnumFwd<P>& o) {
-  // Bernoulli(phi) with the in-place clamps of pert_model.py:622-623
-  float phic = phi_raw;
-  bool mphi = true;
-  if (phic < 0.001f) { phic = 0.001f; mphi = false; }
-  if (phic > 0.999f) { phic = 0.999f; mphi = false; }
+// The 2P joint scores s(c, r) of one (bin, cell): clamped log pi~_c + clamped log Bern(r | phi)
+// + the NB term of chi = c (1 + r).  This is the only place the score is defined; enum_forward
+// (gradient and decode, reference form) and enum_posterior (the marginals) both consume it, so
+// the posterior describes the model the decode maximises.  The scores s(c, r), at s[r * P + c]
+// (r-major like the oracle's (2, P) layout), are the caller's own array and not a member: as a
+// member the posterior kernel loses waves per SIMD at P = 6, 7 and 9, and so it does with the
+// mask formed where nobody reads it (WANT_B = false); both measured, DESIGN.md 6i.
+template <int P>
+struct EnumScores {
+  float Bc[2 * P - 1];   // d NB(chi) / dD = chi (log(1-lam) + Psi), 0 where delta is clamped (WANT_B only)
+  float pi[P];           // softmax(z)
+  float zmax;            // max_k z_k
+  float lse1p;           // log1p(sum_{k != jmax} exp(z_k - zmax))
+  float om;              // 1 - pi_jmax summed from the other states
+  float phic;            // phi clamped to [0.001, 0.999]
+  uint32_t mk;           // bit k: pi_k inside the clamp_probs range, the gradient's mask (WANT_B only)
+  int jmax;              // first argmax_k z_k
+  bool mphi;             // phi inside its clamps
+};
+
+template <int P, bool WANT_B>
+PERT_HD void enum_scores(float x, float invx, const float (&z)[P], float log1m_lam, float D,
+                         float phi_raw, float (&s)[2 * P], EnumScores<P>& q) {
+  float (&Bc)[2 * P - 1] = q.Bc;
+  // Bernoulli(phi) with the in-place clamps of pert_model.py:622-623; the mask is open where
+  // the clamp left phi as it was (as obs_pair_cellbin)
+  const float phic = fmed3(phi_raw, 0.001f, 0.999f);
+  const bool mphi = phic == phi_raw;
+  q.phic = phic;
+  q.mphi = mphi;
   const float lphi = flog(phic);
   const float l1mphi = flog(1.0f - phic);
 
@@ -391,38 +413,36 @@ PERT_HD void enum_forward(float x, float invx, const float (&z)[P], float log1m_
   float t = 0.0f;
 #pragma unroll
   for (int k = 0; k < P; ++k) {
-    o.pi[k] = (k == jmax) ? 1.0f : fexp(z[k] - m);
-    t += (k == jmax) ? 0.0f : o.pi[k];
+    q.pi[k] = (k == jmax) ? 1.0f : fexp(z[k] - m);
+    t += (k == jmax) ? 0.0f : q.pi[k];
   }
   const float inv1t = frcp(1.0f + t);
   const float lse1p = log1p_corr(t, inv1t);
-  o.zmax = m;
-  o.lse1p = lse1p;
-  o.jmax = jmax;
-  o.om = t * inv1t;
-  // joint scores s(c, r): r-major like the oracle's (2, P) layout
-  float s[2 * P];
+  q.zmax = m;
+  q.lse1p = lse1p;
+  q.jmax = jmax;
+  q.om = t * inv1t;
   uint32_t mk = 0;
 #pragma unroll
   for (int k = 0; k < P; ++k) {
-    const float e = o.pi[k];
+    const float e = q.pi[k];
     const float pk = e * inv1t;
-    o.pi[k] = pk;
+    q.pi[k] = pk;
     const float om = (k == jmax) ? t * inv1t : 1.0f - pk;
     const bool hi = om < kEps32;
     const bool lo = pk < kEps32;
-    mk |= (hi || lo) ? 0u : (1u << k);
+    if (WANT_B) mk |= (hi || lo) ? 0u : (1u << k);
     const float lc = hi ? kLog1mEps32 : (lo ? kLogEps32 : (z[k] - m) - lse1p);
     s[k] = lc + l1mphi;
     s[P + k] = lc + lphi;
   }
+  q.mk = mk;
 
   // negative-binomial part per distinct chi, folded straight into the scores
   const float n_clamped = log1m_lam + lambda_delta1(x, invx);   // delta == 1 (chi == 0 or chi D < 1)
-  float Bc[2 * P - 1];
   s[0] += n_clamped;
   s[P] += n_clamped;
-  Bc[0] = 0.0f;
+  if (WANT_B) Bc[0] = 0.0f;
   if (D >= kAsymMin) {
     // every delta = chi D >= kAsymMin: straight-line asymptotic series, no clamp, no shift --
     // one basic block, so the 2P-2 independent chains interleave (ILP)
@@ -435,7 +455,7 @@ PERT_HD void enum_forward(float x, float invx, const float (&z)[P], float log1m_
       float lam, psi;
       nb_lgdiff_asym_hoisted(d, rD * (1.0f / (float)chi), x, ldx + kLogInt[chi], lam, psi);
       const float nchi = d * log1m_lam + lam;
-      Bc[chi] = (float)chi * (log1m_lam + psi);
+      if (WANT_B) Bc[chi] = (float)chi * (log1m_lam + psi);
       if (chi < P) s[chi] += nchi;
       if ((chi % 2) == 0) s[P + chi / 2] += nchi;
     }
@@ -447,17 +467,35 @@ PERT_HD void enum_forward(float x, float invx, const float (&z)[P], float log1m_
       float nchi;
       if (d < 1.0f) {
         nchi = n_clamped;
-        Bc[chi] = 0.0f;
+        if (WANT_B) Bc[chi] = 0.0f;
       } else {
         float lam, psi;
         nb_lgdiff(d, x, invx, lam, psi);
         nchi = d * log1m_lam + lam;
-        Bc[chi] = (float)chi * (log1m_lam + psi);
+        if (WANT_B) Bc[chi] = (float)chi * (log1m_lam + psi);
       }
       if (chi < P) s[chi] += nchi;
       if ((chi % 2) == 0) s[P + chi / 2] += nchi;
     }
   }
+}
+
+// The reference form of the enumerated cell.bin: host self-tests only (enum_cellbin,
+// pert_selftest_enum_cellbin_host); no kernel instantiates it -- the passes use enum_online.
+template <int P, bool WANT_GRAD, bool WANT_ARGMAX>
+PERT_HD void enum_forward(float x, float invx, const float (&z)[P], float log1m_lam, float D,
+                          float phi_raw, EnumFwd<P>& o) {
+  EnumScores<P> q;
+  float s[2 * P];
+  enum_scores<P, WANT_GRAD>(x, invx, z, log1m_lam, D, phi_raw, s, q);
+  const float (&Bc)[2 * P - 1] = q.Bc;
+  const uint32_t mk = q.mk;
+  o.zmax = q.zmax;
+  o.lse1p = q.lse1p;
+  o.jmax = q.jmax;
+  o.om = q.om;
+#pragma unroll
+  for (int k = 0; k < P; ++k) o.pi[k] = q.pi[k];
 
   float smax = -INFINITY;
   int amax = 0;
@@ -482,7 +520,7 @@ PERT_HD void enum_forward(float x, float invx, const float (&z)[P], float log1m_
     sgm += gm;
   }
   o.gD = gD;
-  o.gt = mphi ? (g1 - phic) : 0.0f;
+  o.gt = q.mphi ? (g1 - q.phic) : 0.0f;
   o.sgm = sgm;
 }
 
@@ -1017,81 +1055,15 @@ PERT_HD float clipped_sigmoid(float zz, float* dmask) {
 //   p_rep = sum_c gamma(c, 1)   (the return value)   and   p_cn[k] = gamma(k, 0) + gamma(k, 1),
 // UNMASKED -- EnumFwd::gcm / gt carry the clamp masks of the gradient and are not these.  The
 // Dirichlet prior does not enter: given pi the discrete posterior has no eta term.
-// The scores are built exactly as enum_forward builds them (clamped log pi~, clamped
-// Bernoulli(phi), the NB term per distinct chi with the asymptotic branch for D >= kAsymMin and
-// the delta < 1 clamp otherwise): those ~50 lines are DUPLICATED here on purpose, so that
-// enum_forward / enum_online and the code objects of the step and decode kernels stay exactly
-// as they are; folding both into one shared score builder is a later clean-up.
+// The scores are enum_scores', the ones enum_forward takes its argmax of.
 // se is summed per cn state (e(k, 0) + e(k, 1), then over k), so sum_k p_cn[k] = 1 within
 // (P + 2) eps32; both outputs are kept in [0, 1] (the reciprocal is good to an ulp only).
 template <int P>
 PERT_HD float enum_posterior(float x, float invx, const float (&z)[P], float log1m_lam, float D, float phi_raw,
                              float (&p_cn)[P]) {
-  // Bernoulli(phi) with the in-place clamps of pert_model.py:622-623
-  const float phic = fmed3(phi_raw, 0.001f, 0.999f);
-  const float lphi = flog(phic);
-  const float l1mphi = flog(1.0f - phic);
-
-  // pi = softmax(z) and log(clamp_probs(pi)), as enum_forward
-  float m = z[0];
-  int jmax = 0;
-#pragma unroll
-  for (int k = 1; k < P; ++k) { if (z[k] > m) { m = z[k]; jmax = k; } }
-  float e[P];
-  float t = 0.0f;
-#pragma unroll
-  for (int k = 0; k < P; ++k) {
-    e[k] = (k == jmax) ? 1.0f : fexp(z[k] - m);
-    t += (k == jmax) ? 0.0f : e[k];
-  }
-  const float inv1t = frcp(1.0f + t);
-  const float lse1p = log1p_corr(t, inv1t);
+  EnumScores<P> q;
   float s[2 * P];
-#pragma unroll
-  for (int k = 0; k < P; ++k) {
-    const float pk = e[k] * inv1t;
-    const float om = (k == jmax) ? t * inv1t : 1.0f - pk;
-    const bool hi = om < kEps32;
-    const bool lo = pk < kEps32;
-    const float lc = hi ? kLog1mEps32 : (lo ? kLogEps32 : (z[k] - m) - lse1p);
-    s[k] = lc + l1mphi;
-    s[P + k] = lc + lphi;
-  }
-
-  // negative-binomial part per distinct chi, folded straight into the scores
-  const float n_clamped = log1m_lam + lambda_delta1(x, invx);   // delta == 1 (chi == 0 or chi D < 1)
-  s[0] += n_clamped;
-  s[P] += n_clamped;
-  if (D >= kAsymMin) {
-    const float rD = frcp(D);
-    const float ldx = x > 0.0f ? flog(D) - flog(x) : 0.0f;
-#pragma unroll
-    for (int chi = 1; chi < 2 * P - 1; ++chi) {
-      if (!chi_needed<P>(chi)) continue;
-      const float d = (float)chi * D;
-      float lam, psi;
-      nb_lgdiff_asym_hoisted(d, rD * (1.0f / (float)chi), x, ldx + kLogInt[chi], lam, psi);
-      const float nchi = d * log1m_lam + lam;
-      if (chi < P) s[chi] += nchi;
-      if ((chi % 2) == 0) s[P + chi / 2] += nchi;
-    }
-  } else {
-#pragma unroll
-    for (int chi = 1; chi < 2 * P - 1; ++chi) {
-      if (!chi_needed<P>(chi)) continue;
-      const float d = (float)chi * D;
-      float nchi;
-      if (d < 1.0f) {
-        nchi = n_clamped;
-      } else {
-        float lam, psi;
-        nb_lgdiff(d, x, invx, lam, psi);
-        nchi = d * log1m_lam + lam;
-      }
-      if (chi < P) s[chi] += nchi;
-      if ((chi % 2) == 0) s[P + chi / 2] += nchi;
-    }
-  }
+  enum_scores<P, false>(x, invx, z, log1m_lam, D, phi_raw, s, q);
 
   // gamma = softmax of the 2P scores; the marginals
   float smax = s[0];

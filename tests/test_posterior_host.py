@@ -119,6 +119,29 @@ def test_posterior_ties_to_the_hot_path_responsibilities(nat, P):
     assert (fwd["gt"][~open_] == 0).all()                # masked there: not the posterior
 
 
+@pytest.mark.parametrize("P", [2, 5, 13, 16])
+def test_joint_argmax_carries_its_share_of_the_posterior(nat, P):
+    """The decode's joint argmax a = r* P + c* (enum_forward) and the marginals (enum_posterior)
+    come from one score: the largest of 2P softmax weights is at least 1 / (2P), and each
+    marginal that contains the argmax state is at least that weight, less the (P + 2) eps32 of
+    the normalisation (sum_k p_cn[k] = 1 within that much)."""
+    x, z, D, phi = _inputs(P)
+    n = x.size
+    em1 = np.zeros((n, P), np.float32)
+    fwd = nat.selftest_enum_cellbin_host(P, x, em1, em1.sum(1), z, np.log1p(-LAM), D, phi)
+    out = nat.selftest_enum_posterior_host(P, x, z, np.log1p(-LAM), D, phi)
+    a = fwd["argmax"]
+    assert a.min() >= 0 and a.max() < 2 * P
+    c, r = a % P, a // P
+    assert (r == 1).any() and (r == 0).any() and np.unique(c).size > 1
+    floor = 1.0 / (2 * P) - (P + 2) * 2.0 ** -23
+    p_c = out["p_cn"].astype(np.float64)[np.arange(n), c]
+    p_rep = out["p_rep"].astype(np.float64)
+    p_r = np.where(r == 1, p_rep, 1.0 - p_rep)
+    assert (p_c >= floor).all(), (float(p_c.min()), floor)
+    assert (p_r >= floor).all(), (float(p_r.min()), floor)
+
+
 def _problem(nat, **kw):
     d = dict(kind=2, L=10, N=10, P=13, K1=5, n_libs=1, ldn=256)
     d.update(kw)
