@@ -462,6 +462,48 @@ int pert_rt_binarize(int32_t L, int32_t N, const double* x, const pert_bin_param
                      double* covs, int8_t* gmm_state, uint8_t* rt_state, double* dist, int32_t* best,
                      int32_t* n_rep, int32_t* flags, hipStream_t stream);
 
+/* The cell-cycle-classifier features of compute_ccc_features.py:18-56 for every cell of one length
+ * in ONE launch, one workgroup per cell, in fp64 (ccc_features.py):
+ *   score1  GaussianMixture(n_components=1).fit(x).score(x): mean = sum x / (L + 10 eps),
+ *           var = sum (x - mean)^2 / (L + 10 eps) + reg_covar, the mean log density
+ *   score2  GaussianMixture(n_components=2): KMeans tolerance, centring, k-means++ from this cell's
+ *           own draws, Lloyd, EM, then the mean log probability under the FINAL parameters
+ *   lrs     -2 (score1 - score2)
+ *   madn    median |x[i+1] - x[i]| over the L - 1 adjacent pairs in row order (radix select: the
+ *           order statistics themselves, (a + b) / 2 for an even count: np.median's bits)
+ *   breakpoints  # i with state[i] != state[i-1] and chrom[i] == chrom[i-1]
+ * Every sum is a fixed-order block sum, so reruns are bit-identical.
+ *
+ * The random stream: the reference fits with random_state=None, so each cell consumes 4 doubles
+ * of numpy's global generator in sorted-cell order: d0 -> first1 (the 1-component k-means++
+ * choice; unused by the arithmetic, carried so the ABI documents the stream), d1 -> first2 (the
+ * 2-component choice: searchsorted(cdf of L equal weights, d1, 'right')), d2, d3 -> u (the two
+ * local-trial uniforms).  The caller draws them and passes them per cell. */
+typedef struct {
+  int32_t lloyd_max_iter;          /* 300 */
+  int32_t em_max_iter;             /* 100 */
+  double em_tol;                   /* 1e-3 */
+  double reg_covar;                /* 1e-6 */
+  /* margins, with the meaning of pert_bin_params' */
+  double pp_margin;
+  double tie_margin;
+  double lloyd_margin;
+  double em_margin;
+} pert_ccc_params;
+
+/* x: double [N][L], one contiguous row per cell in that cell's own row order (device).
+ * first1, first2: int32 [N]; u: double [N][2].  state, chrom: int32 [N][L], or both null (no
+ * breakpoints: zeros are written).  scratch: int8 [2][N][L] (Lloyd's labels).  Outputs (device,
+ * the caller's): score1, score2, lrs, madn double [N]; breakpoints int32 [N]; flags int32 [N]:
+ * PERT_BIN_F_PP / PERT_BIN_F_LLOYD / PERT_BIN_F_EM (the caller recomputes a flagged cell's scores
+ * on the host; madn and breakpoints are exact either way).
+ * PERT_E_ARG for L < 2, N < 1, a null required buffer, exactly one of state / chrom null, or an
+ * iteration count < 1.  Allocates nothing. */
+int pert_ccc_features(int32_t L, int32_t N, const double* x, const int32_t* first1, const int32_t* first2,
+                      const double* u, const int32_t* state, const int32_t* chrom, const pert_ccc_params* p,
+                      int8_t* scratch, double* score1, double* score2, double* lrs, double* madn,
+                      int32_t* breakpoints, int32_t* flags, hipStream_t stream);
+
 /* ---- Downstream replication-timing analyses (rt_profiles.py) on the decode's rep_out.
  * rep is uint8 [L][ldn] (0 / 1 per (bin, cell); ldn >= N a multiple of 16, the base 16-byte
  * aligned; columns n >= N hold undefined bytes and are never counted).  group is int32 [N]: the

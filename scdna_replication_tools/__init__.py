@@ -6,8 +6,9 @@ module of this package is the reference module of the same name (file:line cited
 its docstring) and binds the MI355X implementation in ``scdna_replication_tools_amd``:
 the PERT fits (steps 1-3, decode) run through libpert_hip.so on the GPU; there is no
 CPU fallback.  Modules of the reference outside the PERT hot path (plotting, the
-deterministic 'cell' / 'clone' / 'bulk' levels, CCC / SPF analyses) are not provided
-(DESIGN.md section 8); the pseudobulk and T-width analyses of the decode are
+deterministic 'cell' / 'clone' levels, the SPF analysis) are not provided
+(DESIGN.md section 8); the cell-cycle-classifier features are (``compute_ccc_features``,
+DESIGN.md section 6j); the pseudobulk and T-width analyses of the decode are
 (``compute_pseudobulk_rt_profiles``, ``calculate_twidth``), and so is the read-count simulator
 upstream of the fit (``pert_simulator``: the reference's generative model drawn by a HIP
 sampler).

@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = (
     "pert_comm_inject_fault", "pert_finalize_shared", "pert_finalize_cells", "pert_comm_set_options",
     "pert_comm_overlap", "pert_comm_allreduce_async", "pert_comm_join", "pert_rt_counts", "pert_rt_tfs_hist",
     "pert_sim_raw", "pert_sim_cells", "pert_sim_reads", "pert_sim_normalise", "pert_rt_binarize",
-    "pert_enum_posterior", "pert_selftest_enum_posterior_host",
+    "pert_enum_posterior", "pert_selftest_enum_posterior_host", "pert_ccc_features",
 )
 
 # include/pert_hip.h status codes of a sharded fit's communicator
@@ -111,6 +111,12 @@ class PertBinParams(ctypes.Structure):
                 ("pp_margin", c_double), ("tie_margin", c_double), ("lloyd_margin", c_double),
                 ("em_margin", c_double), ("gap_margin", c_double), ("skew_margin", c_double),
                 ("resp_margin", c_double), ("thresh_margin", c_double), ("dist_margin", c_double)]
+
+
+class PertCccParams(ctypes.Structure):
+    _fields_ = [("lloyd_max_iter", c_int32), ("em_max_iter", c_int32), ("em_tol", c_double), ("reg_covar", c_double),
+                ("pp_margin", c_double), ("tie_margin", c_double), ("lloyd_margin", c_double),
+                ("em_margin", c_double)]
 
 
 class PertAdamHparams(ctypes.Structure):
@@ -236,6 +242,9 @@ def load(path: str, gil: bool = True):
                                          c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_binarize.argtypes = [i32, i32, c_void_p, POINTER(PertBinParams), c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    handle.pert_ccc_features.argtypes = [i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         POINTER(PertCccParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]
     handle.pert_rt_counts.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_tfs_hist.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i32, i32,
                                         i32, c_void_p, c_void_p, c_void_p]

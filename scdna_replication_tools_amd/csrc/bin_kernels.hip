@@ -21,6 +21,7 @@
 namespace {
 
 using namespace gmm2;
+using namespace gmm2::f64;   // Cell, assign2, lloyd
 
 constexpr int kNT = PERT_BIN_THRESHOLDS;
 constexpr int kTG = 10;                 // thresholds per scan pass
@@ -34,72 +35,6 @@ struct EmConsts {
   __device__ __forceinline__ double em_margin() const { return s_par[kEmMargin]; }
   __device__ __forceinline__ double reg_covar() const { return s_par[kRegCovar]; }
 };
-
-struct Cell {
-  const double* x;     // the cell's profile, [L]
-  int L;
-  double mX;           // its mean (KMeans centres its data first)
-  __device__ __forceinline__ double X(int i) const { return x[i]; }
-  __device__ __forceinline__ double Xc(int i) const { return x[i] - mX; }
-};
-
-// sklearn's label rule for 2 centres: centre 1 where ||c1||^2 - 2 x c1 < ||c0||^2 - 2 x c0.
-// *near: the two sides are within `tie` of each other, relative to their magnitude.
-__device__ __forceinline__ int assign2(double X, double c0, double c1, double tie, bool* near) {
-  const double d1 = c1 * c1 - 2.0 * X * c1;
-  const double d0 = c0 * c0 - 2.0 * X * c0;
-  const double scale = c0 * c0 + c1 * c1 + 2.0 * fabs(X) * (fabs(c0) + fabs(c1));
-  *near = fabs(d1 - d0) <= tie * scale;
-  return d1 < d0 ? 1 : 0;
-}
-
-// Lloyd's k-means for 2 centres (sklearn _kmeans_single_lloyd: at most max_iter iterations, stop
-// on unchanged labels or a centre shift <= tol, then the final re-assignment).  lab_old: scratch
-// row; out: the final labels.  *fragile: the shift test within lloyd_margin of tol, or a point
-// of an iteration within tie_margin of the assignment boundary.
-__device__ void lloyd(const Cell& c, double c0, double c1, double tol, double sumXc, const pert_bin_params& p,
-                      int8_t* lab_old, int8_t* out, bool* fragile, double* sm) {
-  const int L = c.L;
-  for (int i = threadIdx.x; i < L; i += kT) lab_old[i] = -1;
-  bool strict = false;
-  for (int it = 0; it < p.lloyd_max_iter; ++it) {
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};       // w1, s1, changed labels, points on the boundary
-    for (int i = threadIdx.x; i < L; i += kT) {
-      const double X = c.Xc(i);
-      bool near;
-      const int l = assign2(X, c0, c1, p.tie_margin, &near);
-      acc[0] += (double)l;
-      acc[1] += l ? X : 0.0;
-      acc[2] += (l != lab_old[i]) ? 1.0 : 0.0;
-      acc[3] += near ? 1.0 : 0.0;
-      lab_old[i] = (int8_t)l;
-    }
-    block_sums<4>(acc, sm);
-    const double w1 = acc[0], w0 = (double)L - w1;
-    const double s1 = acc[1], s0 = sumXc - s1;
-    const double n0 = w0 > 0.0 ? s0 / fmax(w0, 1.0) : c0;
-    const double n1 = w1 > 0.0 ? s1 / fmax(w1, 1.0) : c1;
-    const double shift = (n0 - c0) * (n0 - c0) + (n1 - c1) * (n1 - c1);
-    const bool same = acc[2] == 0.0;
-    if (acc[3] > 0.0) *fragile = true;
-    if (!same && fabs(shift - tol) <= p.lloyd_margin * tol) *fragile = true;
-    c0 = n0;
-    c1 = n1;
-    if (same) {
-      strict = true;
-      break;
-    }
-    if (shift <= tol) break;
-  }
-  double nr[1] = {0.0};
-  for (int i = threadIdx.x; i < L; i += kT) {
-    bool near = false;
-    out[i] = strict ? lab_old[i] : (int8_t)assign2(c.Xc(i), c0, c1, p.tie_margin, &near);
-    nr[0] += near ? 1.0 : 0.0;
-  }
-  block_sums<1>(nr, sm);
-  if (nr[0] > 0.0) *fragile = true;
-}
 
 __global__ __launch_bounds__(kT) void rt_binarize_kernel(int L, int N, const double* __restrict__ x,
                                                             pert_bin_params p, double* __restrict__ means,

@@ -1,5 +1,5 @@
-// gmm2_stages.h -- the stages tau_kernels.hip and bin_kernels.hip share: sklearn's
-// GaussianMixture(n_components=2, random_state=0) on one 1-D profile per 256-thread workgroup
+// gmm2_stages.h -- the stages tau_kernels.hip, bin_kernels.hip and ccc_kernels.hip share: sklearn's
+// GaussianMixture(n_components=2) on one 1-D profile per 256-thread workgroup, from the caller's draws
 // (k-means++ for two centres, EM from the k-means labels, the mixture's per-point log
 // probabilities), the two binary levels (the GMM means, or np.percentile order statistics chosen
 // by the skew), and the fixed-order block reductions, prefix scan and radix select under them.
@@ -7,13 +7,15 @@
 // Every stage is in fp64 and every sum a fixed-order block sum, so reruns are bit-identical; the
 // decisions are sklearn's / numpy's, and each reports whether it sat within the caller's rounding
 // margin (the caller routes such a cell to its exact host path).  Each kernel keeps what differs
-// in substance: its Cell, its prologue, its assign2 / lloyd and its threshold scan.  The stage
-// functions are plain __device__ templates, as each kernel's lloyd is: every one has a single call
-// site per kernel and is inlined there.
+// in substance: its prologue and what it does with the fit (a threshold scan, or
+// ccc_kernels.hip's scores); tau_kernels.hip also its own Cell, assign2 and lloyd, while the two
+// fp64 row kernels share those of namespace f64 below.  The stage functions are plain __device__
+// templates: every one has a single call site per kernel and is inlined there.
 //
 // Cell: c.L bins, c.X(i) the profile the mixture is fitted to, c.Xc(i) the centred profile
-// k-means runs on.  Params: pert_tau_params or pert_bin_params (the fields used here carry the
-// same names in both).  sm: LDS of at least the widest block sum's NV * kTW doubles.
+// k-means runs on.  Params: pert_tau_params, pert_bin_params or a kernel's per-cell view (the
+// fields used here carry the same names in all).  sm: LDS of at least the widest block sum's
+// NV * kTW doubles.
 
 #pragma once
 
@@ -390,6 +392,81 @@ inline bool params_ok(int L, const Params& p) {
     if (p.q_lo[j] < 0 || p.q_lo[j] >= L || p.q_hi[j] < 0 || p.q_hi[j] >= L) return false;
   return true;
 }
+
+// The fp64 row kernels' (bin_kernels.hip, ccc_kernels.hip) Cell, label rule and Lloyd.  In a
+// namespace of their own: tau_kernels.hip keeps a Cell / assign2 / lloyd of the same names on its
+// standardised fp32 reads.
+namespace f64 {
+
+struct Cell {
+  const double* x;     // the cell's profile, [L]
+  int L;
+  double mX;           // its mean (KMeans centres its data first)
+  __device__ __forceinline__ double X(int i) const { return x[i]; }
+  __device__ __forceinline__ double Xc(int i) const { return x[i] - mX; }
+};
+
+// sklearn's label rule for 2 centres: centre 1 where ||c1||^2 - 2 x c1 < ||c0||^2 - 2 x c0.
+// *near: the two sides are within `tie` of each other, relative to their magnitude.
+__device__ __forceinline__ int assign2(double X, double c0, double c1, double tie, bool* near) {
+  const double d1 = c1 * c1 - 2.0 * X * c1;
+  const double d0 = c0 * c0 - 2.0 * X * c0;
+  const double scale = c0 * c0 + c1 * c1 + 2.0 * fabs(X) * (fabs(c0) + fabs(c1));
+  *near = fabs(d1 - d0) <= tie * scale;
+  return d1 < d0 ? 1 : 0;
+}
+
+// Lloyd's k-means for 2 centres (sklearn _kmeans_single_lloyd: at most max_iter iterations, stop
+// on unchanged labels or a centre shift <= tol, then the final re-assignment).  lab_old: scratch
+// row; out: the final labels.  *fragile: the shift test within lloyd_margin of tol, or a point
+// of an iteration within tie_margin of the assignment boundary.  Params: pert_bin_params or
+// pert_ccc_params (lloyd_max_iter, tie_margin, lloyd_margin).
+template <class Params>
+__device__ void lloyd(const Cell& c, double c0, double c1, double tol, double sumXc, const Params& p,
+                      int8_t* lab_old, int8_t* out, bool* fragile, double* sm) {
+  const int L = c.L;
+  for (int i = threadIdx.x; i < L; i += kT) lab_old[i] = -1;
+  bool strict = false;
+  for (int it = 0; it < p.lloyd_max_iter; ++it) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};       // w1, s1, changed labels, points on the boundary
+    for (int i = threadIdx.x; i < L; i += kT) {
+      const double X = c.Xc(i);
+      bool near;
+      const int l = assign2(X, c0, c1, p.tie_margin, &near);
+      acc[0] += (double)l;
+      acc[1] += l ? X : 0.0;
+      acc[2] += (l != lab_old[i]) ? 1.0 : 0.0;
+      acc[3] += near ? 1.0 : 0.0;
+      lab_old[i] = (int8_t)l;
+    }
+    block_sums<4>(acc, sm);
+    const double w1 = acc[0], w0 = (double)L - w1;
+    const double s1 = acc[1], s0 = sumXc - s1;
+    const double n0 = w0 > 0.0 ? s0 / fmax(w0, 1.0) : c0;
+    const double n1 = w1 > 0.0 ? s1 / fmax(w1, 1.0) : c1;
+    const double shift = (n0 - c0) * (n0 - c0) + (n1 - c1) * (n1 - c1);
+    const bool same = acc[2] == 0.0;
+    if (acc[3] > 0.0) *fragile = true;
+    if (!same && fabs(shift - tol) <= p.lloyd_margin * tol) *fragile = true;
+    c0 = n0;
+    c1 = n1;
+    if (same) {
+      strict = true;
+      break;
+    }
+    if (shift <= tol) break;
+  }
+  double nr[1] = {0.0};
+  for (int i = threadIdx.x; i < L; i += kT) {
+    bool near = false;
+    out[i] = strict ? lab_old[i] : (int8_t)assign2(c.Xc(i), c0, c1, p.tie_margin, &near);
+    nr[0] += near ? 1.0 : 0.0;
+  }
+  block_sums<1>(nr, sm);
+  if (nr[0] > 0.0) *fragile = true;
+}
+
+}  // namespace f64
 
 // The status of the launch just made.
 inline int launch_status() {
