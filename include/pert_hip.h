@@ -361,6 +361,32 @@ int pert_stream_ceiling(const pert_problem* prob, pert_state* st, hipStream_t st
 int pert_enum_posterior(const pert_problem* prob, const pert_state* st, const uint8_t* cn_state,
                         float* rep_prob, float* cn_prob, float* cn_marg, hipStream_t stream);
 
+/* Posterior draws of the enumerated latent states at the current parameters (steps 2/3,
+ * post_kernels.hip): whole-matrix realisations from the posterior gamma(c, r) that
+ * pert_enum_posterior gives the marginals of and the decode the argmax of
+ * (infer_discrete(temperature=1)).  Reads what pert_enum_posterior reads; nothing in st is written.
+ * Per element the weights e(c, r) = exp(s(c, r) - max s) and their inclusive running sums C_j over
+ * the joint states in the order j = 2 c + r (cn-major, rep inner) are formed once; S = C_{2P-1}.
+ * A draw with uniform u in (0, 1) is the FIRST j with u S < C_j (strict: a state whose weight
+ * underflowed to 0 is never drawn); if rounding leaves no such j, the last state with e > 0.
+ * Random numbers follow THE COUNTER RULE below with stream tag PERT_TAG_DRAWS: draw g (global
+ * index first_draw + d) of (bin l, global cell cell0 + n) takes word g & 3 of
+ *   philox(counter = {l, low word of the cell index, g >> 2, high word of the cell index})
+ * so one Philox call serves four consecutive draws and a draw depends only on (seed, bin, global
+ * cell, g): not on the grid, the tile size, how first_draw / n_draws chunk the draws or which cells
+ * a launch holds.  The uniform is ((w >> 8) + 0.5) 2^-24 rounded to fp32 and kept below 1.
+ *   rep_draw  uint8 [n_draws][L][ldn]  rep = j & 1 of draw first_draw + d in plane d   (required)
+ *   cn_draw   uint8 [n_draws][L][ldn]  cn = j >> 1                                     (or NULL)
+ * Each plane is a contiguous [L][ldn] matrix in the decode's encodings.  Columns n >= N are left
+ * untouched.  No atomics, no cross-lane sums: reruns are bit-identical.  Argument checks, all
+ * before any launch: pert_enum_posterior's, in its order (a null rep_draw for its null rep_prob);
+ * then PERT_E_ARG for n_draws outside [1, PERT_MAX_DRAWS], first_draw < 0, first_draw + n_draws
+ * above INT32_MAX or cell0 < 0; then for more than 65535 bin tiles. */
+#define PERT_TAG_DRAWS 3u
+#define PERT_MAX_DRAWS 4096
+int pert_enum_draw(const pert_problem* prob, const pert_state* st, uint64_t seed, int64_t cell0,
+                   int32_t first_draw, int32_t n_draws, uint8_t* rep_draw, uint8_t* cn_draw, hipStream_t stream);
+
 /* tau initialiser (guess_times, pert_model.py:426-457): the batched pass of
  * manhattan_binarization (:364-423) for every cell in ONE launch, in fp64 -- standardisation,
  * GaussianMixture(n_components=2, random_state=0) (k-means++ and Lloyd initialisation, then EM),
@@ -545,6 +571,7 @@ int pert_rt_tfs_hist(int32_t L, int32_t N, int32_t ldn, int32_t G, const uint8_t
  * simulated in several launches (cell0) get the numbers one launch over all of them gives.
  * A uniform is ((w >> 8) + 0.5) 2^-24 rounded to fp32 and kept below 1 (the one value that
  * rounds to 1.0 becomes 1 - 2^-24): strictly inside (0, 1).
+ * (Tags 1 and 2 are the simulator's streams; 3 is PERT_TAG_DRAWS, pert_enum_draw.)
  * Stream PERT_SIM_TAG_CELLS (bin index 0): draw round 0 word 0 -> tau; draw round 1 + k words
  * 0, 1 -> beta k = mean + std sqrt(-2 ln u1) cos(2 pi u2), with u = ((w >> 8) + 0.5) 2^-24 and
  * the arithmetic in fp64, rounded to fp32 once.
@@ -610,6 +637,11 @@ int pert_selftest_enum_online_host(int32_t P, int64_t n, const float* x, const f
  * x, D, phi float [n], z float [n][P] -> p_rep float [n], p_cn float [n][P]. */
 int pert_selftest_enum_posterior_host(int32_t P, int64_t n, const float* x, const float* z, float log1m_lam,
                                       const float* D, const float* phi, float* p_rep, float* p_cn /* [n][P] */);
+/* pert_enum_draw's per-element arithmetic (pert_math.h enum_draw_cdf / enum_draw_pick) on the host:
+ * x, D, phi float [n], z float [n][P], u float [n][n_draws] in (0, 1) -> cn, rep uint8 [n][n_draws]. */
+int pert_selftest_enum_draw_host(int32_t P, int64_t n, const float* x, const float* z, float log1m_lam,
+                                 const float* D, const float* phi, int32_t n_draws, const float* u /* [n][n_draws] */,
+                                 uint8_t* cn, uint8_t* rep);
 
 const char* pert_version(void);
 

@@ -11,5 +11,7 @@ deterministic 'cell' / 'clone' levels, the SPF analysis) are not provided
 DESIGN.md section 6j); the pseudobulk and T-width analyses of the decode are
 (``compute_pseudobulk_rt_profiles``, ``calculate_twidth``), and so is the read-count simulator
 upstream of the fit (``pert_simulator``: the reference's generative model drawn by a HIP
-sampler).
+sampler).  ``scRT(..., posterior_draws=n)`` additionally leaves n posterior
+draws of the S-phase states on ``scrt.model.draws_s`` (no reference counterpart beyond
+``infer_discrete(temperature=1)``).
 """

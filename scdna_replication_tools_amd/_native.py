@@ -24,6 +24,7 @@ MIN_P, MAX_P = 2, 16
 BLOCK = 256
 RT_MAX_GROUPS, RT_MAX_EDGES = 32, 257      # pert_rt_tfs_hist
 SIM_TAG_CELLS, SIM_TAG_READS = 1, 2        # pert_sim_*: the stream tags of the counter rule
+TAG_DRAWS, MAX_DRAWS = 3, 4096             # pert_enum_draw: its stream tag, and the draws of one call
 
 # every symbol include/pert_hip.h declares
 EXPORTED_SYMBOLS = (
@@ -37,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "pert_comm_overlap", "pert_comm_allreduce_async", "pert_comm_join", "pert_rt_counts", "pert_rt_tfs_hist",
     "pert_sim_raw", "pert_sim_cells", "pert_sim_reads", "pert_sim_normalise", "pert_rt_binarize",
     "pert_enum_posterior", "pert_selftest_enum_posterior_host", "pert_ccc_features",
+    "pert_enum_draw", "pert_selftest_enum_draw_host",
 )
 
 # include/pert_hip.h status codes of a sharded fit's communicator
@@ -238,6 +240,9 @@ def load(path: str, gil: bool = True):
     handle.pert_enum_posterior.argtypes = [POINTER(PertProblem), POINTER(PertState), c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p]
     handle.pert_selftest_enum_posterior_host.argtypes = [i32, i64, fp, fp, c_float, fp, fp, fp, fp]
+    handle.pert_enum_draw.argtypes = [POINTER(PertProblem), POINTER(PertState), c_uint64, i64, i32, i32, c_void_p,
+                                      c_void_p, c_void_p]
+    handle.pert_selftest_enum_draw_host.argtypes = [i32, i64, fp, fp, c_float, fp, fp, i32, fp, c_void_p, c_void_p]
     handle.pert_tau_binarize.argtypes = [i32, i32, c_void_p, POINTER(PertTauParams), c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_binarize.argtypes = [i32, i32, c_void_p, POINTER(PertBinParams), c_void_p, c_void_p, c_void_p,
@@ -361,3 +366,19 @@ def selftest_enum_posterior_host(P, x, z, log1m_lam, D, phi):
                                                   _fptr(p_rep), _fptr(p_cn)),
           "pert_selftest_enum_posterior_host")
     return dict(p_rep=p_rep, p_cn=p_cn)
+
+
+def selftest_enum_draw_host(P, x, z, log1m_lam, D, phi, u):
+    """Host evaluation of pert_math.h enum_draw_cdf / enum_draw_pick (test-only): the drawn cn and
+    rep states, uint8 [n][n_draws], of each element for the uniforms u float32 [n][n_draws]."""
+    import numpy as np
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    x, z, D, phi, u = map(f, (x, z, D, phi, u))
+    n = x.size
+    u = u.reshape(n, -1)
+    cn = np.empty(u.shape, np.uint8)
+    rep = np.empty(u.shape, np.uint8)
+    check(lib().pert_selftest_enum_draw_host(P, n, _fptr(x), _fptr(z), float(log1m_lam), _fptr(D), _fptr(phi),
+                                             u.shape[1], _fptr(u), cn.ctypes.data, rep.ctypes.data),
+          "pert_selftest_enum_draw_host")
+    return dict(cn=cn, rep=rep)

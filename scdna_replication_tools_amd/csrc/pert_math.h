@@ -1084,4 +1084,49 @@ PERT_HD float enum_posterior(float x, float invx, const float (&z)[P], float log
   return fminf(g1 * inv_se, 1.0f);
 }
 
+// ----------------------------------------------------------------- posterior draws of one cell.bin
+// Draws from the same posterior (post_kernels.hip; infer_discrete(temperature=1), where the decode
+// is temperature=0).  enum_draw_cdf forms, once per element, the unnormalised weights
+// e(c, r) = exp(s(c, r) - max s) and their inclusive running sums C_j over the joint states in the
+// fixed order j = 2 c + r (cn-major, rep inner: the order enum_posterior sums its q_c in); the
+// total is S = C[2P - 1].  It returns the last state with e > 0 (the argmax has e = 1, so there is
+// one).  enum_draw_pick maps a uniform u in (0, 1) to the FIRST j with u S < C_j -- strict, so a
+// state whose weight underflowed to 0 (C_j == C_{j-1}) is never drawn; if rounding of u S leaves
+// no such j, the draw is that last state with e > 0.  The scores are a local array of
+// enum_draw_cdf (as in enum_posterior) and every index below is a constant after unrolling: C
+// lives in registers and the pick is a running compare (C is nondecreasing, so the first j with
+// t < C_j is the number of j with C_j <= t), not an indexed local array.
+template <int P>
+PERT_HD int enum_draw_cdf(float x, float invx, const float (&z)[P], float log1m_lam, float D, float phi_raw,
+                          float (&C)[2 * P]) {
+  EnumScores<P> q;
+  float s[2 * P];
+  enum_scores<P, false>(x, invx, z, log1m_lam, D, phi_raw, s, q);
+  float smax = s[0];
+#pragma unroll
+  for (int i = 1; i < 2 * P; ++i) smax = fmaxf(smax, s[i]);
+  float run = 0.0f;
+  int jlast = 0;
+#pragma unroll
+  for (int c = 0; c < P; ++c) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const float e = fexp(s[r * P + c] - smax);
+      run += e;
+      C[2 * c + r] = run;
+      jlast = (e > 0.0f) ? 2 * c + r : jlast;
+    }
+  }
+  return jlast;
+}
+
+template <int P>
+PERT_HD int enum_draw_pick(const float (&C)[2 * P], int jlast, float u) {
+  const float t = u * C[2 * P - 1];
+  int j = 0;
+#pragma unroll
+  for (int i = 0; i < 2 * P - 1; ++i) j += (C[i] <= t) ? 1 : 0;
+  return (t < C[2 * P - 1]) ? j : jlast;
+}
+
 }  // namespace pert

@@ -680,6 +680,7 @@ class PertShard:
         self.cn_out = torch.zeros((L, ldn), dtype=torch.uint8, device=dev)
         self.rep_out = torch.zeros((L, ldn), dtype=torch.uint8, device=dev)
         self.rep_prob = self.cn_prob = self.cn_marg = None     # posterior()'s outputs, allocated on first use
+        self.rep_draw = self.cn_draw = None                    # draw_states()'s planes, likewise
 
         self.pass_events = None      # list -> (start, end) HIP events around every pass
         self.pass_event_stride = 1   # (one-rank loop) events around every stride-th iteration's pass
@@ -1288,4 +1289,33 @@ class PertShard:
         out = {"rep_prob": self.rep_prob[:, :N], "cn_prob": self.cn_prob[:, :N]}
         if cn_marginal:
             out["cn_marg"] = self.cn_marg[:, :, :N]
+        return out
+
+    def draw_states(self, n_draws: int, seed: int = 0, first_draw: int = 0, cell0: int = 0, want_cn: bool = True):
+        """Draws from the posterior of the enumerated states at the current parameters
+        (pert_enum_draw; infer_discrete(temperature=1), where ``decode()`` is temperature=0):
+        ``rep`` (and with ``want_cn`` ``cn``), (n_draws, L, N) uint8 in ``decode()``'s encodings,
+        plane d holding draw ``first_draw + d``.  A draw depends only on (seed, bin, global cell
+        ``cell0 + n``, draw index): chunks of draws, and shards of cells given their ``cell0``,
+        reproduce one call over all of them.  Device tensors, allocated on first use and reused
+        while the shape holds: the next call overwrites them."""
+        if self.kind == nat.KIND_STEP1:
+            raise ValueError("step 1 has no latent discrete sites")
+        n_draws, seed = int(n_draws), int(seed)
+        if not 1 <= n_draws <= nat.MAX_DRAWS:
+            raise ValueError("n_draws must be in [1, {}]".format(nat.MAX_DRAWS))
+        shape = (n_draws, self.L, self.ldn)
+        if self.rep_draw is None or tuple(self.rep_draw.shape) != shape:
+            self.rep_draw = self.cn_draw = None
+            self.rep_draw = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+        if want_cn and self.cn_draw is None:
+            self.cn_draw = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+        cn = self.cn_draw if want_cn else None
+        with self._dev():
+            nat.check(self.lib.pert_enum_draw(ctypes.byref(self._prob), ctypes.byref(self._state),
+                                              seed & 0xFFFFFFFFFFFFFFFF, int(cell0), int(first_draw), n_draws,
+                                              _ptr(self.rep_draw), _ptr(cn), self._stream()), "pert_enum_draw")
+        out = {"rep": self.rep_draw[:, :, :self.N]}
+        if want_cn:
+            out["cn"] = cn[:, :, :self.N]
         return out

@@ -40,7 +40,7 @@ import pandas as pd
 import torch
 
 from . import prep
-from ._native import KIND_STEP1, KIND_STEP2, KIND_STEP3
+from ._native import KIND_STEP1, KIND_STEP2, KIND_STEP3, MAX_DRAWS
 from .engine import CanonicalPiBlock, EtaCodebook, PertShard
 from .init import init_params
 from .sharding import cell_bounds, make_allreduce
@@ -179,7 +179,7 @@ class pert_infer_scRT():
                  max_iter_step1=None, min_iter_step1=None, max_iter_step3=None, min_iter_step3=None,
                  cuda=False, seed=0, P=13, K=4, J=5, upsilon=6, run_step3=True, *, device=None,
                  init_method='sampled', dirichlet_mode='torch32', n_jobs=1, tau_init_method='batched',
-                 process_group=None, log_steps=True, posterior=False):
+                 process_group=None, log_steps=True, posterior_draws=0, draws_seed=None, posterior=False):
         self.cn_s = cn_s
         self.cn_g1 = cn_g1
         self.input_col = input_col
@@ -231,6 +231,15 @@ class pert_infer_scRT():
         # model_rep_prob = P(rep = 1) and model_cn_prob = P(cn = model_cn_state) (no reference
         # counterpart; PertShard.posterior)
         self.posterior = bool(posterior)
+        # posterior_draws > 0: that many whole-matrix draws of the S-phase (cn, rep) states from the
+        # posterior the decode maximises (PertShard.draw_states), left as a PosteriorDraws in
+        # ``draws_s`` after run_pert_model(); draws_seed None = seed.  The returned frames do not
+        # change.  Step 3's G1/2 states are not drawn.
+        self.posterior_draws = int(posterior_draws)
+        if not 0 <= self.posterior_draws <= MAX_DRAWS:
+            raise ValueError("posterior_draws must be in [0, {}]".format(MAX_DRAWS))
+        self.draws_seed = seed if draws_seed is None else draws_seed
+        self.draws_s = None
         self.timings = {}
         self.iters = {}
         self.launched = {}
@@ -503,6 +512,22 @@ class pert_infer_scRT():
                 c[k] = dd.gather_cells(post[k].cpu().numpy())
         return cn, rep, c
 
+    def _draw(self, shard: PertShard, dd: _Dist, cell0: int):
+        """``posterior_draws`` draws of this fit's states, each plane gathered over the ranks as
+        the MAP states are: (rep, cn), uint8 (n_draws, loci, cells) on the host."""
+        out = shard.draw_states(self.posterior_draws, seed=self.draws_seed, cell0=cell0)
+        return tuple(np.stack([dd.gather_cells(out[k][d].cpu().numpy()) for d in range(self.posterior_draws)])
+                     for k in ("rep", "cn"))
+
+    def _posterior_draws(self, planes, inp):
+        """The PosteriorDraws of the S-phase fit, labelled in the order of its output."""
+        from .posterior_draws import PosteriorDraws
+        clones = None
+        if self.clone_col is not None and self.clone_col in self.cn_s.columns:
+            clones = prep.first_clone(self.cn_s, inp.cells_s, self.cell_col, self.clone_col, inp.keys_s)
+        return PosteriorDraws(planes[0], inp.cells_s, np.asarray(inp.loci_chr).astype(str), inp.loci_start,
+                              clone_ids=clones, cn=planes[1])
+
     def run_pert_model(self):
         t_all = time.perf_counter()
         P, K = self.P, self.K
@@ -628,11 +653,13 @@ class pert_infer_scRT():
             mark("step2")
             tic = time.perf_counter()
             cn_map, rep_map, c2 = self._decode(s2, dd)
+            planes_s = self._draw(s2, dd, cells_s.start) if self.posterior_draws > 0 else None
             trace_s = MapTrace(cn=cn_map, rep=rep_map, expose_u=c2["expose_u"], expose_rho=c2["expose_rho"],
                                expose_a=c2["expose_a"], expose_tau=c2["expose_tau"],
                                **{k: c2[k] for k in ("rep_prob", "cn_prob") if k in c2})
             cn_s_out, supp_s_out_df = self.package_s_output(
                 self.cn_s, trace_s, self._axes(inp.cells_s, inp.keys_s), lambda_fit, losses_g, losses_s)
+            self.draws_s = self._posterior_draws(planes_s, inp) if planes_s is not None else None
             self.timings["decode_package_s"] = time.perf_counter() - tic
             rho_fit = c2["expose_rho"]
             a_fit = c2["expose_a"]
