@@ -558,6 +558,44 @@ int pert_rt_tfs_hist(int32_t L, int32_t N, int32_t ldn, int32_t G, const uint8_t
                      const void* hours, const void* f10, const void* edges, int32_t n_edges, int32_t is_f64,
                      int32_t per_cell, uint32_t* hist_n, uint32_t* hist_rep, hipStream_t stream);
 
+/* ---- Per-cell quality features of the phase calls (phase_matrix.py; reference
+ * predict_cycle_phase.py:23-88) on the decode's state matrices and the shard's reads, in place.
+ * The series of cell n is column n of the matrix in row order, t = 0 .. L - 1; the lags are
+ * k = 1 .. max_lag <= PERT_PHASE_MAX_LAG (the reference: 50, averaging lags 9..50).  Matrices follow
+ * the pert_rt_* conventions: rows ldn elements apart, ldn >= N a multiple of 16, the base 16-byte
+ * aligned, columns n >= N undefined and never read.  Both entry points return PERT_E_ARG for a null
+ * or misaligned argument, N < 1, max_lag outside [1, PERT_PHASE_MAX_LAG], L <= max_lag, or L >= 2^20
+ * (the host's n^3 integer arithmetic stays inside int64).  They allocate nothing. */
+#define PERT_PHASE_MAX_LAG 64
+
+/* The integer counts.  rep (and cn, or null: then cn_bk / cn0 are not touched and may be null) are
+ * uint8 [n_planes][L][ldn], the planes plane_stride bytes apart (a multiple of 16, >= L * ldn; not
+ * read when n_planes = 1): the layout of draw_states.  rep counts as replicated where non-zero.
+ * Outputs are uint32 with a leading plane axis and are ADDED to (register sums, then integer
+ * atomics: exact, identical from run to run); the caller zeroes them.
+ *   rep_sum [planes][N]            T = sum_t x_t
+ *   rep_bk, cn_bk [planes][N]      # t with a change between t and t + 1
+ *   cn0 [planes][N]                # t with cn = 0
+ *   rep_lag [planes][max_lag][N]   S_k = #{t < L - k : x_t = x_{t+k} = 1}, row k - 1
+ *   rep_head, rep_tail [planes][max_lag][N]   the sum of the first k and of the last k states
+ * The bins are cut into chunks of whole 64-bin words (>= 2 words; about 1024 waves in all); a chunk
+ * reads the word before its first as the halo. */
+int pert_phase_counts(int32_t L, int32_t N, int32_t ldn, int32_t n_planes, int64_t plane_stride,
+                      const uint8_t* rep, const uint8_t* cn, int32_t max_lag, uint32_t* rep_sum,
+                      uint32_t* rep_bk, uint32_t* cn_bk, uint32_t* cn0, uint32_t* rep_lag, uint32_t* rep_head,
+                      uint32_t* rep_tail, hipStream_t stream);
+
+/* The float series (the reads): x is float [L][ldn], or double when is_f64.  Outputs fp64 (device):
+ * mean [N], and c [max_lag + 1][N] with c_k = sum_{t < L - k} (x_t - m)(x_{t+k} - m).  Two passes
+ * inside the call (the mean, then the centred products; no raw moments), fp64 throughout, no
+ * floating-point atomics: per-chunk partials in the workspace are added in chunk order, so two runs
+ * agree bit for bit.  A NaN or Inf in a cell's series makes that cell's outputs NaN and no other's.
+ * workspace: device, 8-byte aligned, at least pert_phase_acf_workspace() bytes
+ * (= 8 * n_chunks * (max_lag + 2) * N); its contents need not be initialised. */
+int pert_phase_acf_workspace(int32_t L, int32_t N, int32_t max_lag, int64_t* bytes);
+int pert_phase_acf(int32_t L, int32_t N, int32_t ldn, const void* x, int32_t is_f64, int32_t max_lag,
+                   double* mean, double* c, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- Read-count simulator (pert_simulator.py; reference pert_simulator.py:38-282): the
  * generative model run forwards, one Bernoulli and one negative-binomial draw per (bin, cell).
  *

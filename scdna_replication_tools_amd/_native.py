@@ -25,6 +25,7 @@ BLOCK = 256
 RT_MAX_GROUPS, RT_MAX_EDGES = 32, 257      # pert_rt_tfs_hist
 SIM_TAG_CELLS, SIM_TAG_READS = 1, 2        # pert_sim_*: the stream tags of the counter rule
 TAG_DRAWS, MAX_DRAWS = 3, 4096             # pert_enum_draw: its stream tag, and the draws of one call
+PHASE_MAX_LAG = 64                         # pert_phase_counts / pert_phase_acf
 
 # every symbol include/pert_hip.h declares
 EXPORTED_SYMBOLS = (
@@ -39,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "pert_sim_raw", "pert_sim_cells", "pert_sim_reads", "pert_sim_normalise", "pert_rt_binarize",
     "pert_enum_posterior", "pert_selftest_enum_posterior_host", "pert_ccc_features",
     "pert_enum_draw", "pert_selftest_enum_draw_host",
+    "pert_phase_counts", "pert_phase_acf_workspace", "pert_phase_acf",
 )
 
 # include/pert_hip.h status codes of a sharded fit's communicator
@@ -253,6 +255,10 @@ def load(path: str, gil: bool = True):
     handle.pert_rt_counts.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_tfs_hist.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i32, i32,
                                         i32, c_void_p, c_void_p, c_void_p]
+    handle.pert_phase_counts.argtypes = [i32, i32, i32, i32, i64, c_void_p, c_void_p, i32, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    handle.pert_phase_acf_workspace.argtypes = [i32, i32, i32, POINTER(i64)]
+    handle.pert_phase_acf.argtypes = [i32, i32, i32, c_void_p, i32, i32, c_void_p, c_void_p, c_void_p, i64, c_void_p]
     u32 = c_uint32
     handle.pert_sim_raw.argtypes = [u32, u32, u32, u32, u32, u32, i64, c_void_p, c_void_p]
     handle.pert_sim_cells.argtypes = [i32, i32, i32, i64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -181,8 +181,9 @@ class scRT:
         self.min_iter_step1 = int(self.min_iter / 2) if min_iter_step1 is None else min_iter_step1
         self.max_iter_step3 = int(self.max_iter / 2) if max_iter_step3 is None else max_iter_step3
         self.min_iter_step3 = int(self.min_iter / 2) if min_iter_step3 is None else min_iter_step3
-        # pert_infer_scRT's keyword-only arguments (device, posterior, posterior_draws, draws_seed, ...):
-        # after infer() the model, with draws_s when posterior_draws > 0, is self.model
+        # pert_infer_scRT's keyword-only arguments (device, posterior, posterior_draws, draws_seed,
+        # phase_calls, ...): after infer() the model, with draws_s when posterior_draws > 0 and
+        # phase_table when phase_calls, is self.model
         self.engine_kwargs = engine_kwargs
 
     def infer(self, level='pert'):

@@ -179,7 +179,8 @@ class pert_infer_scRT():
                  max_iter_step1=None, min_iter_step1=None, max_iter_step3=None, min_iter_step3=None,
                  cuda=False, seed=0, P=13, K=4, J=5, upsilon=6, run_step3=True, *, device=None,
                  init_method='sampled', dirichlet_mode='torch32', n_jobs=1, tau_init_method='batched',
-                 process_group=None, log_steps=True, posterior_draws=0, draws_seed=None, posterior=False):
+                 process_group=None, log_steps=True, posterior_draws=0, draws_seed=None, phase_calls=False,
+                 posterior=False):
         self.cn_s = cn_s
         self.cn_g1 = cn_g1
         self.input_col = input_col
@@ -240,6 +241,14 @@ class pert_infer_scRT():
             raise ValueError("posterior_draws must be in [0, {}]".format(MAX_DRAWS))
         self.draws_seed = seed if draws_seed is None else draws_seed
         self.draws_s = None
+        # phase_calls: also make the phase calls of predict_cycle_phase from each fit's decode while
+        # its shard is alive (PhaseMatrix over the decode's states and the shard's reads, in place):
+        # ``phase_table`` after run_pert_model(), the phase_calls table over the S and G1/2 cells
+        # together with a ``fitted_as`` column 'S' / 'G1/2'.  The returned frames do not change.
+        if not isinstance(phase_calls, (bool, np.bool_)):
+            raise ValueError("phase_calls must be True or False")
+        self.phase_calls = bool(phase_calls)
+        self.phase_table = None
         self.timings = {}
         self.iters = {}
         self.launched = {}
@@ -519,6 +528,20 @@ class pert_infer_scRT():
         return tuple(np.stack([dd.gather_cells(out[k][d].cpu().numpy()) for d in range(self.posterior_draws)])
                      for k in ("rep", "cn"))
 
+    def _phase_matrix(self, shard: PertShard, cell_ids):
+        """The PhaseMatrix of a fit over its last decode and its reads, in place, computed now: the
+        shard's buffers do not outlive it."""
+        from .phase_matrix import PhaseMatrix
+        N = shard.N
+        return PhaseMatrix(shard.rep_out[:, :N], shard.cn_out[:, :N], shard.reads[:, :N], cell_ids,
+                           device=self.device).release()
+
+    def _phase_table(self, mats):
+        from .phase_matrix import phase_calls
+        table = phase_calls([m for _, m in mats])
+        table['fitted_as'] = np.concatenate([np.full(m.N, name, dtype=object) for name, m in mats])
+        return table
+
     def _posterior_draws(self, planes, inp):
         """The PosteriorDraws of the S-phase fit, labelled in the order of its output."""
         from .posterior_draws import PosteriorDraws
@@ -526,7 +549,7 @@ class pert_infer_scRT():
         if self.clone_col is not None and self.clone_col in self.cn_s.columns:
             clones = prep.first_clone(self.cn_s, inp.cells_s, self.cell_col, self.clone_col, inp.keys_s)
         return PosteriorDraws(planes[0], inp.cells_s, np.asarray(inp.loci_chr).astype(str), inp.loci_start,
-                              clone_ids=clones, cn=planes[1])
+                              clone_ids=clones, cn=planes[1], reads=inp.reads_s)
 
     def run_pert_model(self):
         t_all = time.perf_counter()
@@ -534,7 +557,13 @@ class pert_infer_scRT():
         # the device first: the library's communicator is made on the current device
         if self.device.type == "cuda" and self.device.index is not None:
             torch.cuda.set_device(self.device)
+        dist = torch.distributed
+        if (self.phase_calls and dist.is_available() and dist.is_initialized()
+                and dist.get_world_size(self._group) > 1):
+            raise NotImplementedError("phase_calls=True is not implemented for a fit sharded over a process group: "
+                                      "run phase_matrix.PhaseMatrix on the gathered outputs instead")
         dd = _Dist(self._group, device=self.device)
+        phase_mats = []
         # host work that only steps 2/3 need runs on a helper thread: the consensus profiles as
         # soon as the G1/2 table is sorted (while the S table is prepared), the step-2 prior and
         # tau initialisation while step 1 fits, then (during step 2) the step-3 prior and tau
@@ -653,6 +682,8 @@ class pert_infer_scRT():
             mark("step2")
             tic = time.perf_counter()
             cn_map, rep_map, c2 = self._decode(s2, dd)
+            if self.phase_calls:
+                phase_mats.append(('S', self._phase_matrix(s2, np.asarray(inp.cells_s))))
             planes_s = self._draw(s2, dd, cells_s.start) if self.posterior_draws > 0 else None
             trace_s = MapTrace(cn=cn_map, rep=rep_map, expose_u=c2["expose_u"], expose_rho=c2["expose_rho"],
                                expose_a=c2["expose_a"], expose_tau=c2["expose_tau"],
@@ -687,6 +718,8 @@ class pert_infer_scRT():
                 mark("step3")
                 tic = time.perf_counter()
                 cn3, rep3, c3 = self._decode(s3, dd)
+                if self.phase_calls:
+                    phase_mats.append(('G1/2', self._phase_matrix(s3, np.asarray(inp.cells_g))))
                 trace_s2 = MapTrace(cn=cn3, rep=rep3, expose_u=c3["expose_u"], expose_rho=rho_fit, expose_a=a_fit,
                                     expose_tau=c3["expose_tau"],
                                     **{k: c3[k] for k in ("rep_prob", "cn_prob") if k in c3})
@@ -706,6 +739,7 @@ class pert_infer_scRT():
             helper.shutdown(wait=True, cancel_futures=True)
             threads.close()
             dd.close()
+        self.phase_table = self._phase_table(phase_mats) if self.phase_calls else None
         self.timings["total"] = time.perf_counter() - t_all
         return cn_s_out, supp_s_out_df, cn_g1_out, supp_g1_out_df
 

@@ -38,14 +38,18 @@ class PosteriorDraws:
     """``rep`` (and optionally ``cn``): ``(n_draws, L, N)`` uint8 planes, numpy arrays or torch
     tensors on any device (``draw_states``' result: used in place, each plane a ``(L, N)`` view
     whose rows are ``ldn`` apart).  ``cell_ids [N]``, ``chr [L]``, ``start [L]`` and ``clone_ids [N]``
-    (optional) label them as they label an ``RTMatrix``.  ``device`` is passed on to ``RTMatrix``."""
+    (optional) label them as they label an ``RTMatrix``.  ``device`` is passed on to ``RTMatrix``.
+    ``reads`` (optional): the cells' ``(L, N)`` float32 / float64 read depth, which ``phase_table``
+    needs beside the ``cn`` planes."""
 
-    def __init__(self, rep, cell_ids, chr, start, clone_ids=None, cn=None, device: Optional[str] = None):
+    def __init__(self, rep, cell_ids, chr, start, clone_ids=None, cn=None, device: Optional[str] = None, reads=None):
         if len(rep.shape) != 3 or rep.shape[0] < 1:
             raise ValueError("rep must be (n_draws, bins, cells) planes")
         if cn is not None and tuple(cn.shape) != tuple(rep.shape):
             raise ValueError("cn planes do not match rep's shape {}".format(tuple(rep.shape)))
-        self.rep, self.cn = rep, cn
+        if reads is not None and tuple(reads.shape) != tuple(rep.shape[1:]):
+            raise ValueError("reads do not match the planes' shape {}".format(tuple(rep.shape[1:])))
+        self.rep, self.cn, self.reads = rep, cn, reads
         self.n_draws, self.L, self.N = (int(v) for v in rep.shape)
         self.cell_ids = np.asarray(cell_ids)
         self.chr, self.start = np.asarray(chr), np.asarray(start)
@@ -105,3 +109,28 @@ class PosteriorDraws:
             row.update({"popt_{}".format(i): float(v) for i, v in enumerate(popt)})
             rows.append(row)
         return pd.DataFrame(rows)
+
+    def phase_table(self, q: Sequence[float] = DEFAULT_Q, cell_col="cell_id", frac_thresh=0.05, rep_auto_thresh=0.2,
+                    frac_cn0_thresh=0.05) -> pd.DataFrame:
+        """One row per cell (in ``cell_ids`` order): the share of draws in which ``phase_calls`` calls
+        it S / G1/2 / LQ (``share_S``, ``share_G1/2``, ``share_LQ``), the mean and the quantiles ``q``
+        over the draws of ``rep_auto`` and ``cell_frac_rep`` (NaN-propagating: a draw in which the
+        cell's states are constant has no ``rep_auto``), and ``rpm_auto``, which no draw changes.
+        Needs the ``cn`` planes and ``reads``.  One pert_phase_counts launch over all planes and one
+        pert_phase_acf call (phase_matrix.py)."""
+        from . import phase_matrix as pm
+        if self.cn is None or self.reads is None:
+            raise ValueError("phase_table needs the cn planes and reads")
+        counts = pm.counts_of_planes(self.rep, self.cn, pm.MAX_LAG, device=self.device)
+        num, den = pm.rep_auto_rational(counts, self.L, pm.MIN_LAG, pm.MAX_LAG)
+        frac = counts["T"] / float(self.L)
+        phase = pm.call_phases(frac, pm.rep_auto_exceeds(num, den, rep_auto_thresh), counts["cn0"] / float(self.L),
+                               frac_thresh, frac_cn0_thresh)
+        out = {cell_col: self.cell_ids}
+        for name in ('S', 'G1/2', 'LQ'):
+            out["share_" + name] = (phase == name).mean(axis=0)
+        with np.errstate(invalid="ignore"):
+            out.update(_summary(pm._ratio(num, den), q, "rep_auto"))
+        out.update(_summary(frac, q, "cell_frac_rep"))
+        out["rpm_auto"] = pm.reads_auto(self.reads, device=self.device)
+        return pd.DataFrame(out)
