@@ -387,6 +387,39 @@ int pert_enum_posterior(const pert_problem* prob, const pert_state* st, const ui
 int pert_enum_draw(const pert_problem* prob, const pert_state* st, uint64_t seed, int64_t cell0,
                    int32_t first_draw, int32_t n_draws, uint8_t* rep_draw, uint8_t* cn_draw, hipStream_t stream);
 
+/* Per-cell likelihood curves over S-phase time tau at the current parameters (steps 2/3,
+ * curve_kernels.hip).  tau enters an element's 2P joint scores through the Bernoulli term alone, so
+ * with everything but tau held fixed the log marginal of (bin l, cell n) at any tau is
+ *   m_ln(tau) = log((1 - phi) exp(e_0) + phi exp(e_1)),
+ *   phi = clamp(1 / (1 + exp(-a (tau - rho_l))), 0.001, 0.999),
+ *   e_r = log sum_c exp(log pi~_c + NB'(x ; c (1 + r))),  r = 0, 1    (the branch evidences:
+ *         pert_enum_posterior's scores without the Bernoulli term, the same omitted kappa(x)).
+ *
+ * pert_enum_evidence writes the branch evidences, fp32:
+ *   ev  float [2][L][ldn]  plane 0 = e_0, plane 1 = e_1
+ * It reads what pert_enum_posterior reads, in its launch shape (st->bins_per_tile bins per wave),
+ * and writes nothing of st.  Columns n >= N of ev are left untouched.  No atomics, no cross-lane
+ * sums: reruns are bit-identical.  Argument checks, all before any launch: pert_enum_posterior's,
+ * in its order (a null ev for its null rep_prob; there is no cn_state / cn_prob pair).
+ *
+ * pert_tau_curve sums the element marginals over the bins, per cell and grid point:
+ *   grid    float  [G]     values of tau strictly inside (0, 1), ascending (device memory: the
+ *                          caller validates them)
+ *   curve   double [G][N]  curve[g][n] = sum_l m_ln(grid[g])
+ *   at_fit  double [N]     sum_l m_ln(tau_n) at the cell's own fitted tau (clipped sigmoid of its
+ *                          parameter, as the passes form it)
+ * rho and a are the fit's (rho_fixed / a_fixed in step 3).  m is fp32 (pert_math.h tau_mix); the sum
+ * over bins is fp64 and taken in bin order l = 0 .. L-1 for every (g, n), so the result does not
+ * depend on the launch geometry or on how a caller chunks the grid (any split of the grid into
+ * calls gives the bits of one call).  No atomics, no workspace, nothing allocated; reruns are
+ * bit-identical; nothing of st is written.  PERT_E_ARG, before any launch, for a null argument, a
+ * step-1 problem, G outside [1, PERT_TAU_MAX_GRID], L < 1, N < 1, ldn < N or ldn not a multiple of
+ * PERT_BLOCK, a null st->params, or a null rho_fixed in step 3. */
+#define PERT_TAU_MAX_GRID 1024
+int pert_enum_evidence(const pert_problem* prob, const pert_state* st, float* ev, hipStream_t stream);
+int pert_tau_curve(const pert_problem* prob, const pert_state* st, const float* ev, const float* grid, int32_t G,
+                   double* curve, double* at_fit, hipStream_t stream);
+
 /* tau initialiser (guess_times, pert_model.py:426-457): the batched pass of
  * manhattan_binarization (:364-423) for every cell in ONE launch, in fp64 -- standardisation,
  * GaussianMixture(n_components=2, random_state=0) (k-means++ and Lloyd initialisation, then EM),
@@ -680,6 +713,11 @@ int pert_selftest_enum_posterior_host(int32_t P, int64_t n, const float* x, cons
 int pert_selftest_enum_draw_host(int32_t P, int64_t n, const float* x, const float* z, float log1m_lam,
                                  const float* D, const float* phi, int32_t n_draws, const float* u /* [n][n_draws] */,
                                  uint8_t* cn, uint8_t* rep);
+/* The likelihood curve's per-element arithmetic on the host (pert_math.h enum_evidence / tau_mix):
+ * x, D float [n], z float [n][P] -> ev0, ev1 float [n];  ev0, ev1, phi (unclamped) float [n] -> m float [n]. */
+int pert_selftest_enum_evidence_host(int32_t P, int64_t n, const float* x, const float* z, float log1m_lam,
+                                     const float* D, float* ev0, float* ev1);
+int pert_selftest_tau_mix_host(int64_t n, const float* ev0, const float* ev1, const float* phi, float* m);
 
 const char* pert_version(void);
 

@@ -26,6 +26,7 @@ RT_MAX_GROUPS, RT_MAX_EDGES = 32, 257      # pert_rt_tfs_hist
 SIM_TAG_CELLS, SIM_TAG_READS = 1, 2        # pert_sim_*: the stream tags of the counter rule
 TAG_DRAWS, MAX_DRAWS = 3, 4096             # pert_enum_draw: its stream tag, and the draws of one call
 PHASE_MAX_LAG = 64                         # pert_phase_counts / pert_phase_acf
+TAU_MAX_GRID = 1024                        # pert_tau_curve: the grid points of one call
 
 # every symbol include/pert_hip.h declares
 EXPORTED_SYMBOLS = (
@@ -41,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "pert_enum_posterior", "pert_selftest_enum_posterior_host", "pert_ccc_features",
     "pert_enum_draw", "pert_selftest_enum_draw_host",
     "pert_phase_counts", "pert_phase_acf_workspace", "pert_phase_acf",
+    "pert_enum_evidence", "pert_tau_curve", "pert_selftest_enum_evidence_host", "pert_selftest_tau_mix_host",
 )
 
 # include/pert_hip.h status codes of a sharded fit's communicator
@@ -245,6 +247,11 @@ def load(path: str, gil: bool = True):
     handle.pert_enum_draw.argtypes = [POINTER(PertProblem), POINTER(PertState), c_uint64, i64, i32, i32, c_void_p,
                                       c_void_p, c_void_p]
     handle.pert_selftest_enum_draw_host.argtypes = [i32, i64, fp, fp, c_float, fp, fp, i32, fp, c_void_p, c_void_p]
+    handle.pert_enum_evidence.argtypes = [POINTER(PertProblem), POINTER(PertState), c_void_p, c_void_p]
+    handle.pert_tau_curve.argtypes = [POINTER(PertProblem), POINTER(PertState), c_void_p, c_void_p, i32, c_void_p,
+                                      c_void_p, c_void_p]
+    handle.pert_selftest_enum_evidence_host.argtypes = [i32, i64, fp, fp, c_float, fp, fp, fp]
+    handle.pert_selftest_tau_mix_host.argtypes = [i64, fp, fp, fp, fp]
     handle.pert_tau_binarize.argtypes = [i32, i32, c_void_p, POINTER(PertTauParams), c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_binarize.argtypes = [i32, i32, c_void_p, POINTER(PertBinParams), c_void_p, c_void_p, c_void_p,
@@ -372,6 +379,31 @@ def selftest_enum_posterior_host(P, x, z, log1m_lam, D, phi):
                                                   _fptr(p_rep), _fptr(p_cn)),
           "pert_selftest_enum_posterior_host")
     return dict(p_rep=p_rep, p_cn=p_cn)
+
+
+def selftest_enum_evidence_host(P, x, z, log1m_lam, D):
+    """Host evaluation of pert_math.h enum_evidence (test-only): the two branch evidences
+    e_0, e_1 [n] of each element."""
+    import numpy as np
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    x, z, D = map(f, (x, z, D))
+    n = x.size
+    ev0, ev1 = np.empty(n, np.float32), np.empty(n, np.float32)
+    check(lib().pert_selftest_enum_evidence_host(P, n, _fptr(x), _fptr(z), float(log1m_lam), _fptr(D), _fptr(ev0),
+                                                 _fptr(ev1)), "pert_selftest_enum_evidence_host")
+    return ev0, ev1
+
+
+def selftest_tau_mix_host(ev0, ev1, phi):
+    """Host evaluation of pert_math.h tau_mix (test-only): m [n] from the branch evidences and the
+    unclamped phi."""
+    import numpy as np
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    ev0, ev1, phi = map(f, (ev0, ev1, phi))
+    m = np.empty(ev0.size, np.float32)
+    check(lib().pert_selftest_tau_mix_host(ev0.size, _fptr(ev0), _fptr(ev1), _fptr(phi), _fptr(m)),
+          "pert_selftest_tau_mix_host")
+    return m
 
 
 def selftest_enum_draw_host(P, x, z, log1m_lam, D, phi, u):

@@ -391,7 +391,10 @@ struct EnumScores {
   bool mphi;             // phi inside its clamps
 };
 
-template <int P, bool WANT_B>
+// BERN = false leaves the Bernoulli term out of every score (enum_evidence: what remains is
+// the part of the score tau does not enter); the instantiations with BERN = true are the
+// function as it always was.
+template <int P, bool WANT_B, bool BERN = true>
 PERT_HD void enum_scores(float x, float invx, const float (&z)[P], float log1m_lam, float D,
                          float phi_raw, float (&s)[2 * P], EnumScores<P>& q) {
   float (&Bc)[2 * P - 1] = q.Bc;
@@ -401,8 +404,8 @@ PERT_HD void enum_scores(float x, float invx, const float (&z)[P], float log1m_l
   const bool mphi = phic == phi_raw;
   q.phic = phic;
   q.mphi = mphi;
-  const float lphi = flog(phic);
-  const float l1mphi = flog(1.0f - phic);
+  const float lphi = BERN ? flog(phic) : 0.0f;
+  const float l1mphi = BERN ? flog(1.0f - phic) : 0.0f;
 
   // pi = softmax(z) (SoftmaxTransform, transforms.py:951-954) and the Categorical log
   // pmf log(clamp_probs(pi)) (categorical.py:67-71, utils.py clamp_probs)
@@ -433,8 +436,8 @@ PERT_HD void enum_scores(float x, float invx, const float (&z)[P], float log1m_l
     const bool lo = pk < kEps32;
     if (WANT_B) mk |= (hi || lo) ? 0u : (1u << k);
     const float lc = hi ? kLog1mEps32 : (lo ? kLogEps32 : (z[k] - m) - lse1p);
-    s[k] = lc + l1mphi;
-    s[P + k] = lc + lphi;
+    s[k] = BERN ? lc + l1mphi : lc;
+    s[P + k] = BERN ? lc + lphi : lc;
   }
   q.mk = mk;
 
@@ -1082,6 +1085,59 @@ PERT_HD float enum_posterior(float x, float invx, const float (&z)[P], float log
 #pragma unroll
   for (int c = 0; c < P; ++c) p_cn[c] = fminf(p_cn[c] * inv_se, 1.0f);
   return fminf(g1 * inv_se, 1.0f);
+}
+
+// ----------------------------------------------------------------- likelihood curve over tau
+// tau enters an element's 2P scores through the Bernoulli term alone, so with everything else
+// held fixed the element's log marginal at any tau is a two-term mixture of the branch
+// evidences (curve_kernels.hip):
+//   e_r = log sum_c exp(log pi~_c + NB'(c (1 + r))),  r = 0, 1        (enum_evidence)
+//   m(tau) = log((1 - phi) exp(e_0) + phi exp(e_1)),  phi = clamp(phi(tau), 0.001, 0.999)   (tau_mix)
+// The scores are enum_scores' without the Bernoulli term (the same clamped log pi~, the same NB
+// terms, the same omitted kappa(x)).  Each branch is summed from its own maximum, whose
+// exponential is exactly 1, so the sum lies in [1, P] (error bound: DESIGN.md 6m).
+template <int P>
+PERT_HD void enum_evidence(float x, float invx, const float (&z)[P], float log1m_lam, float D, float& e0,
+                           float& e1) {
+  EnumScores<P> q;
+  float s[2 * P];
+  enum_scores<P, false, false>(x, invx, z, log1m_lam, D, 0.5f, s, q);
+  float m0 = s[0], m1 = s[P];
+#pragma unroll
+  for (int c = 1; c < P; ++c) {
+    m0 = fmaxf(m0, s[c]);
+    m1 = fmaxf(m1, s[P + c]);
+  }
+  float t0 = 0.0f, t1 = 0.0f;
+#pragma unroll
+  for (int c = 0; c < P; ++c) {
+    t0 += fexp(s[c] - m0);
+    t1 += fexp(s[P + c] - m1);
+  }
+  e0 = m0 + flog(t0);
+  e1 = m1 + flog(t1);
+}
+
+// m = log((1 - phi) exp(e0) + phi exp(e1)) with phi clamped as enum_scores clamps it, in the
+// overflow-safe form: e1 - e0 reaches hundreds, so the larger of the two branch terms plus
+// log1p(exp(-|difference|)).
+// tau_mix_logs takes the two logarithms of the clamped phi (tau_mix_phi), which depend on the bin
+// and on tau but not on the cell: the curve kernel forms them once per (bin, grid point).
+PERT_HD void tau_mix_phi(float phi_raw, float& l1mphi, float& lphi) {
+  const float phic = fmed3(phi_raw, 0.001f, 0.999f);
+  l1mphi = flog(1.0f - phic);
+  lphi = flog(phic);
+}
+PERT_HD float tau_mix_logs(float e0, float e1, float l1mphi, float lphi) {
+  const float b0 = e0 + l1mphi;
+  const float b1 = e1 + lphi;
+  const float q = fexp(-fabsf(b1 - b0));               // in (0, 1]; 0 once the gap passes ~ 87
+  return fmaxf(b0, b1) + log1p_corr(q, frcp(1.0f + q));
+}
+PERT_HD float tau_mix(float e0, float e1, float phi_raw) {
+  float l1mphi, lphi;
+  tau_mix_phi(phi_raw, l1mphi, lphi);
+  return tau_mix_logs(e0, e1, l1mphi, lphi);
 }
 
 // ----------------------------------------------------------------- posterior draws of one cell.bin

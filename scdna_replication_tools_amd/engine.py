@@ -681,6 +681,7 @@ class PertShard:
         self.rep_out = torch.zeros((L, ldn), dtype=torch.uint8, device=dev)
         self.rep_prob = self.cn_prob = self.cn_marg = None     # posterior()'s outputs, allocated on first use
         self.rep_draw = self.cn_draw = None                    # draw_states()'s planes, likewise
+        self.ev = None                                         # evidence()'s two planes, likewise
 
         self.pass_events = None      # list -> (start, end) HIP events around every pass
         self.pass_event_stride = 1   # (one-rank loop) events around every stride-th iteration's pass
@@ -1290,6 +1291,53 @@ class PertShard:
         if cn_marginal:
             out["cn_marg"] = self.cn_marg[:, :, :N]
         return out
+
+    def evidence(self):
+        """The two branch evidences of every (bin, cell) at the current parameters
+        (pert_enum_evidence): ``ev0`` / ``ev1`` = log sum_c exp(log pi~_c + NB'(c (1 + r))) for
+        r = 0 / 1, the element's joint scores without the Bernoulli term -- everything of the
+        element's marginal that tau does not enter.  (L, N) float32 device views, allocated on
+        first use and reused like ``posterior()``'s: the next call overwrites them."""
+        if self.kind == nat.KIND_STEP1:
+            raise ValueError("step 1 has no latent discrete sites")
+        if self.ev is None:
+            self.ev = torch.zeros((2, self.L, self.ldn), dtype=torch.float32, device=self.device)
+        with self._dev():
+            nat.check(self.lib.pert_enum_evidence(ctypes.byref(self._prob), ctypes.byref(self._state), _ptr(self.ev),
+                                                  self._stream()), "pert_enum_evidence")
+        return {"ev0": self.ev[0, :, :self.N], "ev1": self.ev[1, :, :self.N]}
+
+    def tau_curve(self, grid=None):
+        """Every cell's likelihood curve over tau with everything else held at the current
+        parameters (``evidence()``, then pert_tau_curve): a ``tau_curve.TauCurve`` on the host.
+        ``grid``: values of tau strictly inside (0, 1), ascending (default
+        np.linspace(0.01, 0.99, 99)); ValueError for any other.  The device sums the element log
+        marginals over the bins in fp64; the one other term of the objective that tau enters, the
+        u prior log Normal(u_n ; g_n(tau), g_n(tau) / 10) with g_n = mean_reads_n / ((1 + tau)
+        ploidy_n) (pert_model.py:597-600), is added here in fp64 to the curve and to ``at_fit``;
+        ``likelihood_only`` keeps both without it."""
+        from .tau_curve import TauCurve, _Likelihood, u_prior_logpdf, validate_grid
+        if self.kind == nat.KIND_STEP1:
+            raise ValueError("step 1 has no latent discrete sites")
+        g = validate_grid(grid)
+        G, N = int(g.size), self.N
+        self.evidence()
+        grid_d = torch.as_tensor(g, device=self.device)
+        curve = torch.zeros((G, N), dtype=torch.float64, device=self.device)
+        at_fit = torch.zeros(N, dtype=torch.float64, device=self.device)
+        with self._dev():
+            nat.check(self.lib.pert_tau_curve(ctypes.byref(self._prob), ctypes.byref(self._state), _ptr(self.ev),
+                                              _ptr(grid_d), G, _ptr(curve), _ptr(at_fit), self._stream()),
+                      "pert_tau_curve")
+        lay = self.lay
+        p = self.params.cpu()
+        tau = clipped_sigmoid(p[lay.off_tau:lay.off_tau + N]).numpy()
+        u = p[lay.off_u:lay.off_u + N].numpy()
+        lik = _Likelihood(curve.cpu().numpy(), at_fit.cpu().numpy())
+        mean_reads, ploidy = self.mean_reads.cpu().numpy(), self.ploidy.cpu().numpy()
+        prior = u_prior_logpdf(u, mean_reads, ploidy, g.astype(np.float64)[:, None])
+        prior_fit = u_prior_logpdf(u, mean_reads, ploidy, tau.astype(np.float64))
+        return TauCurve(g, lik.loglik + prior, lik.at_fit + prior_fit, tau, likelihood_only=lik)
 
     def draw_states(self, n_draws: int, seed: int = 0, first_draw: int = 0, cell0: int = 0, want_cn: bool = True):
         """Draws from the posterior of the enumerated states at the current parameters

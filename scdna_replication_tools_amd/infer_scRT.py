@@ -182,8 +182,9 @@ class scRT:
         self.max_iter_step3 = int(self.max_iter / 2) if max_iter_step3 is None else max_iter_step3
         self.min_iter_step3 = int(self.min_iter / 2) if min_iter_step3 is None else min_iter_step3
         # pert_infer_scRT's keyword-only arguments (device, posterior, posterior_draws, draws_seed,
-        # phase_calls, ...): after infer() the model, with draws_s when posterior_draws > 0 and
-        # phase_table when phase_calls, is self.model
+        # phase_calls, tau_curve, ...): after infer() the model, with draws_s when posterior_draws > 0,
+        # phase_table when phase_calls and tau_curve_s / tau_table_s (and _g) when tau_curve, is
+        # self.model
         self.engine_kwargs = engine_kwargs
 
     def infer(self, level='pert'):

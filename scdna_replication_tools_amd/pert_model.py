@@ -44,6 +44,7 @@ from ._native import KIND_STEP1, KIND_STEP2, KIND_STEP3, MAX_DRAWS
 from .engine import CanonicalPiBlock, EtaCodebook, PertShard
 from .init import init_params
 from .sharding import cell_bounds, make_allreduce
+from .tau_curve import validate_grid
 from .tau_init import default_threads, guess_times_batched, host_threads
 
 log = logging.getLogger("scdna_replication_tools_amd.pert_model")
@@ -180,7 +181,7 @@ class pert_infer_scRT():
                  cuda=False, seed=0, P=13, K=4, J=5, upsilon=6, run_step3=True, *, device=None,
                  init_method='sampled', dirichlet_mode='torch32', n_jobs=1, tau_init_method='batched',
                  process_group=None, log_steps=True, posterior_draws=0, draws_seed=None, phase_calls=False,
-                 posterior=False):
+                 tau_curve=False, posterior=False):
         self.cn_s = cn_s
         self.cn_g1 = cn_g1
         self.input_col = input_col
@@ -249,6 +250,18 @@ class pert_infer_scRT():
             raise ValueError("phase_calls must be True or False")
         self.phase_calls = bool(phase_calls)
         self.phase_table = None
+        # tau_curve: True (the default grid) or a grid of tau values: each fit's per-cell likelihood
+        # curve over tau with everything else at the fit (PertShard.tau_curve), built while its
+        # shard is alive: ``tau_curve_s`` / ``tau_table_s`` for step 2's S cells and, when step 3
+        # runs, ``tau_curve_g`` / ``tau_table_g`` for its G1/2 cells (tau_curve.TauCurve and its
+        # table()).  The returned frames do not change.
+        if tau_curve is None or (isinstance(tau_curve, (bool, np.bool_)) and not tau_curve):
+            self.tau_grid = None
+        elif isinstance(tau_curve, (bool, np.bool_)):
+            self.tau_grid = validate_grid(None)
+        else:
+            self.tau_grid = validate_grid(tau_curve)
+        self.tau_curve_s = self.tau_curve_g = self.tau_table_s = self.tau_table_g = None
         self.timings = {}
         self.iters = {}
         self.launched = {}
@@ -536,6 +549,12 @@ class pert_infer_scRT():
         return PhaseMatrix(shard.rep_out[:, :N], shard.cn_out[:, :N], shard.reads[:, :N], cell_ids,
                            device=self.device).release()
 
+    def _tau_curve(self, shard: PertShard, cell_ids):
+        """A fit's likelihood curves over tau and their table, one row per cell in the order of
+        ``cell_ids`` (one rank: the shard holds every cell)."""
+        curve = shard.tau_curve(self.tau_grid)
+        return curve, curve.table(cell_ids=np.asarray(cell_ids))
+
     def _phase_table(self, mats):
         from .phase_matrix import phase_calls
         table = phase_calls([m for _, m in mats])
@@ -562,6 +581,10 @@ class pert_infer_scRT():
                 and dist.get_world_size(self._group) > 1):
             raise NotImplementedError("phase_calls=True is not implemented for a fit sharded over a process group: "
                                       "run phase_matrix.PhaseMatrix on the gathered outputs instead")
+        if (self.tau_grid is not None and dist.is_available() and dist.is_initialized()
+                and dist.get_world_size(self._group) > 1):
+            raise NotImplementedError("tau_curve is not implemented for a fit sharded over a process group: "
+                                      "its tables are not gathered over the ranks")
         dd = _Dist(self._group, device=self.device)
         phase_mats = []
         # host work that only steps 2/3 need runs on a helper thread: the consensus profiles as
@@ -685,6 +708,8 @@ class pert_infer_scRT():
             if self.phase_calls:
                 phase_mats.append(('S', self._phase_matrix(s2, np.asarray(inp.cells_s))))
             planes_s = self._draw(s2, dd, cells_s.start) if self.posterior_draws > 0 else None
+            if self.tau_grid is not None:
+                self.tau_curve_s, self.tau_table_s = self._tau_curve(s2, inp.cells_s)
             trace_s = MapTrace(cn=cn_map, rep=rep_map, expose_u=c2["expose_u"], expose_rho=c2["expose_rho"],
                                expose_a=c2["expose_a"], expose_tau=c2["expose_tau"],
                                **{k: c2[k] for k in ("rep_prob", "cn_prob") if k in c2})
@@ -720,6 +745,8 @@ class pert_infer_scRT():
                 cn3, rep3, c3 = self._decode(s3, dd)
                 if self.phase_calls:
                     phase_mats.append(('G1/2', self._phase_matrix(s3, np.asarray(inp.cells_g))))
+                if self.tau_grid is not None:
+                    self.tau_curve_g, self.tau_table_g = self._tau_curve(s3, inp.cells_g)
                 trace_s2 = MapTrace(cn=cn3, rep=rep3, expose_u=c3["expose_u"], expose_rho=rho_fit, expose_a=a_fit,
                                     expose_tau=c3["expose_tau"],
                                     **{k: c3[k] for k in ("rep_prob", "cn_prob") if k in c3})
