@@ -563,6 +563,45 @@ int pert_ccc_features(int32_t L, int32_t N, const double* x, const int32_t* firs
                       int8_t* scratch, double* score1, double* score2, double* lrs, double* madn,
                       int32_t* breakpoints, int32_t* flags, hipStream_t stream);
 
+/* ---- The bulk G1 GC correction's LOWESS curve (gc_correction.py; reference
+ * bulk_gc_correction.py:60-72: statsmodels' lowess(rpm, gc, xvals=...) with delta = 0) over the
+ * C * L points (x = ux[inv[l]], y[c][l]) of a matrix whose x is a property of the column.
+ *   y    double [C][L], device: one contiguous row per cell.  A non-finite y is no point.
+ *   inv  int32 [L], HOST: the distinct-x index of each bin, in [0, U)
+ *   ux   double [U], HOST: the distinct x, finite and strictly increasing
+ *   xv   double [M], HOST: the finite x the curve is evaluated at
+ * The host arrays are checked, then uploaded into the workspace on `stream`; they must stay valid
+ * until the stream has passed the call.  k = int(frac * n + 1e-10) is the caller's, n the number
+ * of finite points: the bandwidth of a fit at x0 is the k-th smallest |x - x0| over the points,
+ * the weights are tricube times the bisquare robustness weights of `it` earlier rounds (the
+ * median of the absolute residuals is exact: np.median's), and the fit is the weighted local line
+ * at x0 (the weighted mean when the window holds one distinct x).  A fit whose bandwidth is 0 or
+ * whose window carries zero weights only is NaN; when that happens to a fit at a data x of a
+ * robustness round, its points' residuals are NaN, so is their median (np.median's propagation) and
+ * the whole curve is NaN.  k must not exceed the number of finite points (only the caller knows
+ * it before the first pass): a larger k has no k-th neighbour and every fit is NaN.
+ * out: double [M], device.
+ * All of it is fp64 with fixed-order sums and integer atomics only: two runs agree bit for bit.
+ * Every launch of the it + 1 rounds and of the final evaluation is queued on `stream`; nothing
+ * is read back.  workspace: device, 16-byte aligned, at least pert_lowess_workspace() bytes,
+ * contents arbitrary.  PERT_E_ARG, before any launch or copy, for a null argument, C, L, U or M
+ * < 1 (M = 0 is allowed in the workspace query: pert_lowess_absmed's), U > L, C > 32 * 65,535
+ * (the sums pass's chunks of 32 cells are one grid dimension), C * L >= 2^31, an
+ * inv outside [0, U), ux not finite and increasing, xv not finite, k outside [1, C * L], it < 0,
+ * a misaligned or short workspace. */
+int pert_lowess_workspace(int32_t C, int32_t L, int32_t U, int32_t M, int64_t* bytes);
+int pert_lowess_curve(int32_t C, int32_t L, int32_t U, int32_t M, const double* y, const int32_t* inv,
+                      const double* ux, const double* xv, int64_t k, int32_t it, double* out, void* workspace,
+                      int64_t workspace_bytes, hipStream_t stream);
+/* The curve's exact median on its own: med[0], med[1] (device) = the two middle order statistics
+ * (ranks (n - 1) / 2 and n / 2, equal for odd n) of |y[c][l] - fit[inv[l]]| over the finite y, by a
+ * radix select on the values' bit patterns; *n_out (device int64, or null) = n.  Without a finite
+ * y, or with a NaN residual (a NaN fit under a finite y), both are NaN.  fit: double [U], device.  Arguments as
+ * above. */
+int pert_lowess_absmed(int32_t C, int32_t L, int32_t U, const double* y, const int32_t* inv, const double* fit,
+                       double* med, int64_t* n_out, void* workspace, int64_t workspace_bytes,
+                       hipStream_t stream);
+
 /* ---- Downstream replication-timing analyses (rt_profiles.py) on the decode's rep_out.
  * rep is uint8 [L][ldn] (0 / 1 per (bin, cell); ldn >= N a multiple of 16, the base 16-byte
  * aligned; columns n >= N hold undefined bytes and are never counted).  group is int32 [N]: the

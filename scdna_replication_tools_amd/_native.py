@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "pert_enum_draw", "pert_selftest_enum_draw_host",
     "pert_phase_counts", "pert_phase_acf_workspace", "pert_phase_acf",
     "pert_enum_evidence", "pert_tau_curve", "pert_selftest_enum_evidence_host", "pert_selftest_tau_mix_host",
+    "pert_lowess_workspace", "pert_lowess_curve", "pert_lowess_absmed",
 )
 
 # include/pert_hip.h status codes of a sharded fit's communicator
@@ -259,6 +260,12 @@ def load(path: str, gil: bool = True):
     handle.pert_ccc_features.argtypes = [i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          POINTER(PertCccParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p]
+    dp = POINTER(c_double)
+    handle.pert_lowess_workspace.argtypes = [i32, i32, i32, i32, POINTER(i64)]
+    handle.pert_lowess_curve.argtypes = [i32, i32, i32, i32, c_void_p, POINTER(i32), dp, dp, i64, i32, c_void_p,
+                                         c_void_p, i64, c_void_p]
+    handle.pert_lowess_absmed.argtypes = [i32, i32, i32, c_void_p, POINTER(i32), c_void_p, c_void_p, c_void_p,
+                                          c_void_p, i64, c_void_p]
     handle.pert_rt_counts.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_tfs_hist.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i32, i32,
                                         i32, c_void_p, c_void_p, c_void_p]

@@ -7,8 +7,10 @@ profiles of ``assign_col``, assigns every S-phase cell to its best-correlated cl
 When ``clone_col`` is None the G1/2 cells are first clustered by KMeans + BIC
 (cncluster.kmeans_cluster, infer_scRT.py:129-138).  ``infer(level='bulk')`` is the
 deterministic baseline (:245-276): the S-phase reads divided by the G1/2 pseudobulk, then the
-threshold binarisation (binarize.py).  The 'cell' and 'clone' levels need statsmodels' lowess
-and ruptures' change-points, which this build cannot check against the reference; they raise.
+threshold binarisation (binarize.py).  ``infer_clone_level()`` is the deterministic clone level
+(:207-242) with the bulk G1 GC correction's LOWESS curve of gc_correction.py; ``infer(level=
+'clone')`` does not dispatch to it yet and raises, as ``level='cell'`` does, which also needs
+ruptures' change-points.
 """
 from __future__ import annotations
 
@@ -18,6 +20,7 @@ import pandas as pd
 from . import prep, rt_profiles
 from .binarize import binarize_profiles, normalize_by_clone
 from .cncluster import kmeans_cluster
+from .gc_correction import bulk_g1_gc_correction
 from .pert_model import pert_infer_scRT
 
 
@@ -247,9 +250,60 @@ class scRT:
         self.model = model
         return model.run_pert_model()
 
+    def infer_clone_level(self):
+        """infer_scRT.py:207-242, the deterministic clone level: consensus clone profiles of
+        ``assign_col``, the S-phase cells assigned to clones by ``input_col``, the bulk G1 GC
+        correction into ``col2`` (gc_correction.py), the clones' consensus of ``col2``, every S cell
+        divided by its clone's into ``rv_col``, then the threshold binarisation.  Sets
+        ``clone_profiles``, ``clone_profiles_gc_norm`` and ``manhattan_df``."""
+        device = self.engine_kwargs.get("device")
+        self._cluster_g1_cells()
+        self.clone_profiles = consensus_profiles(
+            self.cn_g1, self.assign_col, clone_col=self.clone_col, cell_col=self.cell_col, chr_col=self.chr_col,
+            start_col=self.start_col, cn_state_col=self.cn_state_col)
+        self.cn_s = assign_s_to_clones(self.cn_s, self.clone_profiles, col_name=self.input_col,
+                                       clone_col=self.clone_col, cell_col=self.cell_col, chr_col=self.chr_col,
+                                       start_col=self.start_col)
+        self.cn_s, self.cn_g1 = bulk_g1_gc_correction(
+            self.cn_s, self.cn_g1, input_col=self.input_col, gc_col=self.gc_col, cell_col=self.cell_col,
+            library_col=self.library_col, output_col=self.col2, device=device)
+        # the reference passes clone_col alone here (:229): the other columns are the defaults
+        self.clone_profiles_gc_norm = consensus_profiles(self.cn_g1, self.col2, clone_col=self.clone_col)
+        self.cn_s = normalize_by_clone(self.cn_s, self.clone_profiles_gc_norm, input_col=self.col2,
+                                       clone_col=self.clone_col, output_col=self.rv_col, cell_col=self.cell_col,
+                                       chr_col=self.chr_col, start_col=self.start_col,
+                                       cn_state_col=self.cn_state_col, ploidy_col=self.ploidy_col)
+        self.cn_s, self.manhattan_df = binarize_profiles(
+            self.cn_s, self.rv_col, rs_col=self.rs_col, frac_rt_col=self.frac_rt_col, thresh_col=self.col5,
+            cell_col=self.cell_col, MEAN_GAP_THRESH=0.7, EARLY_S_SKEW_THRESH=0.2, LATE_S_SKEW_THRESH=-0.2,
+            device=device)
+        return self.cn_s
+
     def _pert_model(self) -> pert_infer_scRT:
         """infer_scRT.py:127-161: clustering (clone_col None), consensus clone profiles of
         assign_col, S-phase cells assigned to clones, then the PERT model object."""
+        self._cluster_g1_cells()
+        self.clone_profiles = consensus_profiles(
+            self.cn_g1, self.assign_col, clone_col=self.clone_col, cell_col=self.cell_col, chr_col=self.chr_col,
+            start_col=self.start_col, cn_state_col=self.cn_state_col)
+        self.cn_s = assign_s_to_clones(self.cn_s, self.clone_profiles, col_name=self.assign_col,
+                                       clone_col=self.clone_col, cell_col=self.cell_col, chr_col=self.chr_col,
+                                       start_col=self.start_col)
+        model = pert_infer_scRT(
+            self.cn_s, self.cn_g1, input_col=self.input_col, gc_col=self.gc_col, rt_prior_col=self.rt_prior_col,
+            clone_col=self.clone_col, cell_col=self.cell_col, library_col=self.library_col,
+            assign_col=self.assign_col, chr_col=self.chr_col, start_col=self.start_col,
+            cn_state_col=self.cn_state_col, rs_col=self.rs_col, frac_rt_col=self.frac_rt_col,
+            cn_prior_method=self.cn_prior_method, cn_prior_weight=self.cn_prior_weight,
+            learning_rate=self.learning_rate, max_iter=self.max_iter, min_iter=self.min_iter, rel_tol=self.rel_tol,
+            min_iter_step1=self.min_iter_step1, min_iter_step3=self.min_iter_step3,
+            max_iter_step1=self.max_iter_step1, max_iter_step3=self.max_iter_step3, cuda=self.cuda, seed=self.seed,
+            P=self.P, K=self.K, J=self.J, upsilon=self.upsilon, run_step3=self.run_step3, **self.engine_kwargs)
+        return model
+
+    def _cluster_g1_cells(self):
+        """infer_scRT.py:129-138 / :209-212: without clone labels the G1/2 cells are clustered and
+        ``clone_col`` becomes 'cluster_id'."""
         if self.clone_col is None:
             # no clone labels: KMeans + BIC over the G1/2 cells' assign_col profiles (:129-138)
             piv = prep.pivot_any(self.cn_g1, self.assign_col, self.cell_col, self.chr_col, self.start_col)
@@ -278,20 +332,3 @@ class scRT:
                 self.cn_g1 = self.cn_g1[self.cn_g1["cluster_id"].notna()]
                 self.cn_g1["cluster_id"] = self.cn_g1["cluster_id"].astype(np.int64)
             self.clone_col = 'cluster_id'
-        self.clone_profiles = consensus_profiles(
-            self.cn_g1, self.assign_col, clone_col=self.clone_col, cell_col=self.cell_col, chr_col=self.chr_col,
-            start_col=self.start_col, cn_state_col=self.cn_state_col)
-        self.cn_s = assign_s_to_clones(self.cn_s, self.clone_profiles, col_name=self.assign_col,
-                                       clone_col=self.clone_col, cell_col=self.cell_col, chr_col=self.chr_col,
-                                       start_col=self.start_col)
-        model = pert_infer_scRT(
-            self.cn_s, self.cn_g1, input_col=self.input_col, gc_col=self.gc_col, rt_prior_col=self.rt_prior_col,
-            clone_col=self.clone_col, cell_col=self.cell_col, library_col=self.library_col,
-            assign_col=self.assign_col, chr_col=self.chr_col, start_col=self.start_col,
-            cn_state_col=self.cn_state_col, rs_col=self.rs_col, frac_rt_col=self.frac_rt_col,
-            cn_prior_method=self.cn_prior_method, cn_prior_weight=self.cn_prior_weight,
-            learning_rate=self.learning_rate, max_iter=self.max_iter, min_iter=self.min_iter, rel_tol=self.rel_tol,
-            min_iter_step1=self.min_iter_step1, min_iter_step3=self.min_iter_step3,
-            max_iter_step1=self.max_iter_step1, max_iter_step3=self.max_iter_step3, cuda=self.cuda, seed=self.seed,
-            P=self.P, K=self.K, J=self.J, upsilon=self.upsilon, run_step3=self.run_step3, **self.engine_kwargs)
-        return model
