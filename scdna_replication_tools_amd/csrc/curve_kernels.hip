@@ -8,7 +8,8 @@
 //
 //   pert_enum_evidence  one pass in pert_enum_posterior's shape (one wave per 64-cell tile x bin
 //                       tile, lanes are cells): the P logits and the 2P - 1 NB terms once per
-//                       element, written as the two planes of ev.
+//                       element, written as the two planes of ev.  The walk and the inputs of
+//                       an element are enum_tile.h's, the posterior pass's own.
 //   pert_tau_curve      curve[g][n] = sum_l m_ln(grid[g]) and at_fit[n] = sum_l m_ln(tau_n): a wave
 //                       owns a 64-cell tile and kCurveChunk grid points, keeps their fp64 sums in
 //                       registers and walks ALL bins in order l = 0 .. L-1.  So a sum depends on
@@ -17,78 +18,31 @@
 //                       cross-wave reduction, no atomics, reruns bit-identical.
 //
 // Neither kernel writes anything of pert_state, and neither touches a column n >= N of an output.
-#include "../../include/pert_hip.h"
-#include "pert_math.h"
+#include "enum_tile.h"
 
 #include <math.h>
-#include <stddef.h>
 
 namespace {
 
 using namespace pert;
 
-constexpr int kCurveDefaultLT = 32;   // bins per tile when the state names none (as the posterior pass)
-constexpr int kCurveMaxLT = 64;
 constexpr int kCurveChunk = 4;        // grid points per wave of tau_curve_kernel
 constexpr int kBinBlock = 8;          // bins per block of its walk (loads in flight: 2 kBinBlock rows)
 
-#define PERT_CURVE_P_CASES                                                                      \
-  PERT_CASE(2) PERT_CASE(3) PERT_CASE(4) PERT_CASE(5) PERT_CASE(6) PERT_CASE(7) PERT_CASE(8)    \
-  PERT_CASE(9) PERT_CASE(10) PERT_CASE(11) PERT_CASE(12) PERT_CASE(13) PERT_CASE(14)            \
-  PERT_CASE(15) PERT_CASE(16)
-
-// The launch shape, loads and per-element inputs of enum_posterior_kernel (post_kernels.hip):
-// omega and D by the same operations in the same order; phi is not formed.
+// enum_posterior_kernel's walk (enum_tile.h), so its launch shape, loads and the same x, z and D
+// of an element; a, tau and rho are not read and phi is not formed.
 template <int P>
 __global__ void __launch_bounds__(64, 4) enum_evidence_kernel(pert_problem pr, pert_state st, int LT,
                                                               float* __restrict__ ev) {
-  const int lane = threadIdx.x;
-  const int wt = blockIdx.x, bt = blockIdx.y;
-  const int N = pr.N, K1 = pr.K1, ldn = pr.ldn, L = pr.L;
-  const int n = wt * 64 + lane;                 // < ldn: ldn is N rounded up to a multiple of 256
-  const bool valid = n < N;
-  const int l0 = bt * LT;
-  const int l1 = min(L, l0 + LT);
-  const pert_layout lay = st.lay;
-  const float* __restrict__ params = st.params;
-
-  // cell parameters (padded lanes: u = 0, so D = 0 and every chain is clamped; never stored)
-  const float c0 = (1.0f - pr.lamb) / pr.lamb;
-  const float log1m_lam = pr.log1m_lam;
-  float u = 0.0f;
-  float beta[PERT_MAX_K1];
-#pragma unroll
-  for (int k = 0; k < PERT_MAX_K1; ++k) beta[k] = 0.0f;
-  if (valid) {
-    u = params[lay.off_u + n];
-#pragma unroll
-    for (int k = 0; k < PERT_MAX_K1; ++k)
-      if (k < K1) beta[k] = params[lay.off_beta + k * N + n];
-  }
-  const float ucc = u * c0;
-  const float* __restrict__ zt = st.z_pi + (size_t)wt * L * P * 64 + lane;   // this wave tile's logits
-  const size_t plane = (size_t)L * ldn;
-
-  for (int l = l0; l < l1; ++l) {
-    const float* __restrict__ gl = pr.gcf + (size_t)l * K1;
-    float dot = 0.0f;
-#pragma unroll
-    for (int k = 0; k < PERT_MAX_K1; ++k) dot += (k < K1) ? beta[k] * gl[k] : 0.0f;
-
-    const size_t e = (size_t)l * ldn + n;
-    const float x = pr.reads[e];
-    float z[P];
-#pragma unroll
-    for (int k = 0; k < P; ++k) z[k] = zt[((size_t)l * P + k) * 64];
-
-    const float invx = x > 0.0f ? frcp(x) : 0.0f;
-    const float omega = fexp(dot);                         // pert_model.py:633
-    const float D = ucc * omega;                           // :636-640 (delta = chi D)
+  const EnumTile<P, false> t(pr, st, LT);
+  for (int l = t.l0; l < t.l1; ++l) {
+    EnumElem<P> el;
+    t.load(pr, st, l, el);
     float e0, e1;
-    enum_evidence<P>(x, invx, z, log1m_lam, D, e0, e1);
-    if (valid) {
-      ev[e] = e0;
-      ev[plane + e] = e1;
+    enum_evidence<P>(el.x, el.invx, el.z, t.log1m_lam, el.D, e0, e1);
+    if (t.valid) {
+      ev[el.e] = e0;
+      ev[t.plane + el.e] = e1;
     }
   }
 }
@@ -116,20 +70,13 @@ __global__ void __launch_bounds__(64) tau_curve_kernel(pert_problem pr, pert_sta
   const int N = pr.N, ldn = pr.ldn, L = pr.L;
   const int n = wt * 64 + lane;                 // < ldn
   const bool valid = n < N;
-  const bool frozen = pr.kind == PERT_KIND_STEP3;
   const bool own = chunk == 0;
-  const pert_layout lay = st.lay;
-  const float* __restrict__ params = st.params;
-  const float a_val = frozen ? pr.a_fixed : fexp(params[lay.off_a]);
+  const float a_val = fitted_a(pr, st);
 
   // this lane's (bin of a block, grid point of the chunk); lanes past kBinBlock * kCurveChunk repeat
   const int bi = (lane / kCurveChunk) % kBinBlock;
   const float tg = grid[min(g0 + lane % kCurveChunk, G - 1)];   // (the repeats past G are never stored)
-  float tau = 0.5f;
-  if (valid) {
-    float dm;
-    tau = clipped_sigmoid(params[lay.off_tau + n], &dm);
-  }
+  const float tau = valid ? cell_tau(st, n) : 0.5f;
   double acc[kCurveChunk];
 #pragma unroll
   for (int j = 0; j < kCurveChunk; ++j) acc[j] = 0.0;
@@ -153,13 +100,7 @@ __global__ void __launch_bounds__(64) tau_curve_kernel(pert_problem pr, pert_sta
       n1[i] = p1[o];
     }
     const int lm = min(lb + bi, L - 1);
-    float rho;
-    if (frozen) {
-      rho = pr.rho_fixed[lm];
-    } else {
-      float dm;
-      rho = clipped_sigmoid(params[lay.off_rho + lm], &dm);
-    }
+    const float rho = bin_rho(pr, st, lm);
     float l1mphi, lphi;
     tau_mix_phi(frcp(1.0f + fexp(-a_val * (tg - rho))), l1mphi, lphi);   // the passes' own operations
 #pragma unroll
@@ -204,18 +145,6 @@ int selftest_evidence_host(int64_t n, const float* x, const float* z, float log1
   return PERT_OK;
 }
 
-// pert_enum_posterior's checks, in its order (ev for its rep_prob; no cn_state / cn_prob pair)
-int check_enum_args(const pert_problem* prob, const pert_state* st, const void* out) {
-  if (!prob || !st || !out) return PERT_E_ARG;
-  if (prob->kind != PERT_KIND_STEP2 && prob->kind != PERT_KIND_STEP3) return PERT_E_ARG;
-  if (prob->L < 1 || prob->N < 1 || prob->ldn < prob->N || prob->ldn % PERT_BLOCK != 0) return PERT_E_ARG;
-  if (prob->P < PERT_MIN_P || prob->P > PERT_MAX_P) return PERT_E_UNSUPPORTED_P;
-  if (prob->K1 < 1 || prob->K1 > PERT_MAX_K1) return PERT_E_UNSUPPORTED_K;
-  if (!prob->reads || !prob->gcf || !st->params || !st->z_pi) return PERT_E_ARG;
-  if (prob->kind == PERT_KIND_STEP3 && !prob->rho_fixed) return PERT_E_ARG;
-  return PERT_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -223,21 +152,19 @@ extern "C" {
 int pert_enum_evidence(const pert_problem* prob, const pert_state* st, float* ev, hipStream_t stream) {
   const int rc = check_enum_args(prob, st, ev);
   if (rc != PERT_OK) return rc;
-  int lt = st->bins_per_tile > 0 ? st->bins_per_tile : kCurveDefaultLT;
-  lt = lt > kCurveMaxLT ? kCurveMaxLT : lt;
-  const dim3 grid((unsigned)((prob->N + 63) / 64), (unsigned)((prob->L + lt - 1) / lt));
-  if (grid.y > 65535u) return PERT_E_ARG;
+  const int lt = enum_tile_len(st);
+  dim3 grid;
+  if (!enum_grid(prob, lt, grid)) return PERT_E_ARG;
   switch (prob->P) {
 #define PERT_CASE(PP)                                                                                 \
   case PP:                                                                                            \
     hipLaunchKernelGGL(enum_evidence_kernel<PP>, grid, dim3(64), 0, stream, *prob, *st, lt, ev);      \
     break;
-    PERT_CURVE_P_CASES
+    PERT_ENUM_P_CASES
 #undef PERT_CASE
     default: return PERT_E_UNSUPPORTED_P;
   }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PERT_OK : PERT_E_HIP_BASE + (int)e;
+  return launch_status();
 }
 
 int pert_tau_curve(const pert_problem* prob, const pert_state* st, const float* ev, const float* grid, int32_t G,
@@ -253,8 +180,7 @@ int pert_tau_curve(const pert_problem* prob, const pert_state* st, const float* 
   if (waves > INT32_MAX) return PERT_E_ARG;
   hipLaunchKernelGGL(tau_curve_kernel, dim3((unsigned)waves), dim3(64), 0, stream, *prob, *st, ev, grid, (int)G,
                      n_chunks, curve, at_fit);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? PERT_OK : PERT_E_HIP_BASE + (int)e;
+  return launch_status();
 }
 
 int pert_selftest_enum_evidence_host(int32_t P, int64_t n, const float* x, const float* z, float log1m_lam,
@@ -263,7 +189,7 @@ int pert_selftest_enum_evidence_host(int32_t P, int64_t n, const float* x, const
   switch (P) {
 #define PERT_CASE(PP) \
   case PP: return selftest_evidence_host<PP>(n, x, z, log1m_lam, D, ev0, ev1);
-    PERT_CURVE_P_CASES
+    PERT_ENUM_P_CASES
 #undef PERT_CASE
     default: return PERT_E_UNSUPPORTED_P;
   }

@@ -1259,10 +1259,13 @@ class PertShard:
             loss -= L * self.n_cells_total * lp
         return loss, g
 
-    def decode(self):
-        """MAP (cn, rep) per (bin, cell): infer_discrete(temperature=0) (pert_model.py:820-827)."""
+    def _require_discrete_sites(self):
         if self.kind == nat.KIND_STEP1:
             raise ValueError("step 1 has no latent discrete sites")
+
+    def decode(self):
+        """MAP (cn, rep) per (bin, cell): infer_discrete(temperature=0) (pert_model.py:820-827)."""
+        self._require_discrete_sites()
         self._pass(nat.MODE_DECODE)
         return self.cn_out[:, :self.N], self.rep_out[:, :self.N]
 
@@ -1273,8 +1276,7 @@ class PertShard:
         ``cn_marg`` (P, L, N).  Runs ``decode()`` first, so ``cn_out`` / ``rep_out`` are the
         calls these probabilities belong to.  Device tensors, used in place like ``decode()``'s:
         the next call overwrites them."""
-        if self.kind == nat.KIND_STEP1:
-            raise ValueError("step 1 has no latent discrete sites")
+        self._require_discrete_sites()
         self.decode()
         L, N, ldn = self.L, self.N, self.ldn
         if self.rep_prob is None:
@@ -1298,8 +1300,7 @@ class PertShard:
         r = 0 / 1, the element's joint scores without the Bernoulli term -- everything of the
         element's marginal that tau does not enter.  (L, N) float32 device views, allocated on
         first use and reused like ``posterior()``'s: the next call overwrites them."""
-        if self.kind == nat.KIND_STEP1:
-            raise ValueError("step 1 has no latent discrete sites")
+        self._require_discrete_sites()
         if self.ev is None:
             self.ev = torch.zeros((2, self.L, self.ldn), dtype=torch.float32, device=self.device)
         with self._dev():
@@ -1317,8 +1318,7 @@ class PertShard:
         ploidy_n) (pert_model.py:597-600), is added here in fp64 to the curve and to ``at_fit``;
         ``likelihood_only`` keeps both without it."""
         from .tau_curve import TauCurve, _Likelihood, u_prior_logpdf, validate_grid
-        if self.kind == nat.KIND_STEP1:
-            raise ValueError("step 1 has no latent discrete sites")
+        self._require_discrete_sites()
         g = validate_grid(grid)
         G, N = int(g.size), self.N
         self.evidence()
@@ -1347,8 +1347,7 @@ class PertShard:
         ``cell0 + n``, draw index): chunks of draws, and shards of cells given their ``cell0``,
         reproduce one call over all of them.  Device tensors, allocated on first use and reused
         while the shape holds: the next call overwrites them."""
-        if self.kind == nat.KIND_STEP1:
-            raise ValueError("step 1 has no latent discrete sites")
+        self._require_discrete_sites()
         n_draws, seed = int(n_draws), int(seed)
         if not 1 <= n_draws <= nat.MAX_DRAWS:
             raise ValueError("n_draws must be in [1, {}]".format(nat.MAX_DRAWS))
