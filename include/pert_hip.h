@@ -602,6 +602,38 @@ int pert_lowess_absmed(int32_t C, int32_t L, int32_t U, const double* y, const i
                        double* med, int64_t* n_out, void* workspace, int64_t workspace_bytes,
                        hipStream_t stream);
 
+/* ---- The cell level's change-point search (normalize_cell.py; reference normalize_by_cell.py:45-46
+ * and :73-74: ruptures' KernelCPD(kernel='linear', min_size=2).predict(n_bkps = 2 or 1)), for N
+ * profiles at once.  For a profile Y[0..n): S[0] = 0, S[i] = S[i-1] + Y[i-1] added in bin order,
+ * rinv[k] = 1.0 / k correctly rounded, and
+ *   mode 2:  G(a, b) = (S[a] S[a]) rinv[a] + ((S[b] - S[a]) (S[b] - S[a])) rinv[b - a]
+ *                      + ((S[n] - S[b]) (S[n] - S[b])) rinv[n - b]   over 2 <= a, a + 2 <= b <= n - 2
+ *   mode 1:  G(a) = (S[a] S[a]) rinv[a] + ((S[n] - S[a]) (S[n] - S[a])) rinv[n - a]   over 2 <= a <= n - 2
+ * each operation one IEEE fp64 operation, the terms added left to right, nothing fused.  The
+ * largest G wins; a tie goes to the smallest a, then the smallest b.
+ *   y       double [N][ld], device: one row per cell, its first len[c] entries the profile (finite)
+ *   len     int32 [N], HOST: 0 <= len[c] <= ld
+ *   mode    int32 [N], HOST: 1 or 2 breakpoints
+ *   active  int32 [N], HOST: 1 = searched, 0 = skipped (the cell's outputs are left as they are)
+ *   a, b    int32 [N], device: the breakpoints ([a, b, n] of ruptures; b = len[c] in mode 1);
+ *           a = b = -1 when the search is infeasible (len < 6 in mode 2, < 4 in mode 1)
+ *   gain    double [N], device: the winning G (0 when infeasible)
+ * The host arrays are checked, then uploaded into the workspace on `stream`; they must stay valid
+ * until the stream has passed the call.  Three launches (prefix sums, the search over cells x tiles
+ * of a with S and rinv in LDS, the per-cell reduction of the tiles' winners by (gain, -a, -b)); no
+ * atomics, so the result does not depend on the tiling and two runs agree bit for bit.  ld is at
+ * most PERT_CPD_MAX_N: the two tables of the longest cell, 16 (len + 1) bytes, and 256 bytes of
+ * winners must fit gfx950's 160 KiB of LDS.  workspace: device, 16-byte aligned, at least
+ * pert_cpd_workspace() bytes, contents arbitrary.  PERT_E_ARG, before any launch or copy, for a
+ * null argument, N < 1 or > 65,535 (cells are one grid dimension), ld < 1 or > PERT_CPD_MAX_N, a
+ * len outside [0, ld], a mode other than 1 or 2, an active other than 0 or 1, a misaligned y or
+ * workspace, a short workspace.  Allocates nothing. */
+#define PERT_CPD_MAX_N 10000
+int pert_cpd_workspace(int32_t N, int32_t ld, int64_t* bytes);
+int pert_cpd_search(int32_t N, int32_t ld, const double* y, const int32_t* len, const int32_t* mode,
+                    const int32_t* active, int32_t* a, int32_t* b, double* gain, void* workspace,
+                    int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- Downstream replication-timing analyses (rt_profiles.py) on the decode's rep_out.
  * rep is uint8 [L][ldn] (0 / 1 per (bin, cell); ldn >= N a multiple of 16, the base 16-byte
  * aligned; columns n >= N hold undefined bytes and are never counted).  group is int32 [N]: the

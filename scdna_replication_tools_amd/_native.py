@@ -27,6 +27,7 @@ SIM_TAG_CELLS, SIM_TAG_READS = 1, 2        # pert_sim_*: the stream tags of the 
 TAG_DRAWS, MAX_DRAWS = 3, 4096             # pert_enum_draw: its stream tag, and the draws of one call
 PHASE_MAX_LAG = 64                         # pert_phase_counts / pert_phase_acf
 TAU_MAX_GRID = 1024                        # pert_tau_curve: the grid points of one call
+CPD_MAX_N = 10000                          # pert_cpd_search: the longest profile (PERT_CPD_MAX_N)
 
 # every symbol include/pert_hip.h declares
 EXPORTED_SYMBOLS = (
@@ -44,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "pert_phase_counts", "pert_phase_acf_workspace", "pert_phase_acf",
     "pert_enum_evidence", "pert_tau_curve", "pert_selftest_enum_evidence_host", "pert_selftest_tau_mix_host",
     "pert_lowess_workspace", "pert_lowess_curve", "pert_lowess_absmed",
+    "pert_cpd_workspace", "pert_cpd_search",
 )
 
 # include/pert_hip.h status codes of a sharded fit's communicator
@@ -266,6 +268,9 @@ def load(path: str, gil: bool = True):
                                          c_void_p, i64, c_void_p]
     handle.pert_lowess_absmed.argtypes = [i32, i32, i32, c_void_p, POINTER(i32), c_void_p, c_void_p, c_void_p,
                                           c_void_p, i64, c_void_p]
+    handle.pert_cpd_workspace.argtypes = [i32, i32, POINTER(i64)]
+    handle.pert_cpd_search.argtypes = [i32, i32, c_void_p, POINTER(i32), POINTER(i32), POINTER(i32), c_void_p, c_void_p,
+                                       c_void_p, c_void_p, i64, c_void_p]
     handle.pert_rt_counts.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_tfs_hist.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i32, i32,
                                         i32, c_void_p, c_void_p, c_void_p]

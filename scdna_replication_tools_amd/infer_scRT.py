@@ -8,9 +8,11 @@ When ``clone_col`` is None the G1/2 cells are first clustered by KMeans + BIC
 (cncluster.kmeans_cluster, infer_scRT.py:129-138).  ``infer(level='bulk')`` is the
 deterministic baseline (:245-276): the S-phase reads divided by the G1/2 pseudobulk, then the
 threshold binarisation (binarize.py).  ``infer_clone_level()`` is the deterministic clone level
-(:207-242) with the bulk G1 GC correction's LOWESS curve of gc_correction.py; ``infer(level=
-'clone')`` does not dispatch to it yet and raises, as ``level='cell'`` does, which also needs
-ruptures' change-points.
+(:207-242) with the bulk G1 GC correction's LOWESS curve of gc_correction.py, and
+``infer_cell_level()`` the deterministic cell level (:171-204): the same correction, then every S
+cell normalised by its best-matching G1/2 cell with its cell-specific copy-number changes removed by
+the change-point search of normalize_cell.py.  ``infer(level='clone')`` and ``infer(level='cell')``
+do not dispatch to them yet and raise; the methods are the way in.
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ from . import prep, rt_profiles
 from .binarize import binarize_profiles, normalize_by_clone
 from .cncluster import kmeans_cluster
 from .gc_correction import bulk_g1_gc_correction
+from .normalize_cell import normalize_by_cell
 from .pert_model import pert_infer_scRT
 
 
@@ -277,6 +280,34 @@ class scRT:
             self.cn_s, self.rv_col, rs_col=self.rs_col, frac_rt_col=self.frac_rt_col, thresh_col=self.col5,
             cell_col=self.cell_col, MEAN_GAP_THRESH=0.7, EARLY_S_SKEW_THRESH=0.2, LATE_S_SKEW_THRESH=-0.2,
             device=device)
+        return self.cn_s
+
+    def infer_cell_level(self):
+        """infer_scRT.py:171-204, the deterministic cell level: consensus clone profiles of
+        ``assign_col``, the S-phase cells assigned to clones by ``assign_col`` (:185), the bulk G1 GC
+        correction into ``col2``, every S cell normalised by its best-matching G1/2 cell of the clone
+        into ``col3`` and cleared of cell-specific copy-number changes into ``rv_col`` (``col4`` numbers
+        the nominated segments; normalize_cell.py), then the threshold binarisation.  Sets
+        ``clone_profiles`` and ``manhattan_df``."""
+        device = self.engine_kwargs.get("device")
+        self._cluster_g1_cells()
+        self.clone_profiles = consensus_profiles(
+            self.cn_g1, self.assign_col, clone_col=self.clone_col, cell_col=self.cell_col, chr_col=self.chr_col,
+            start_col=self.start_col, cn_state_col=self.cn_state_col)
+        self.cn_s = assign_s_to_clones(self.cn_s, self.clone_profiles, col_name=self.assign_col,
+                                       clone_col=self.clone_col, cell_col=self.cell_col, chr_col=self.chr_col,
+                                       start_col=self.start_col)
+        self.cn_s, self.cn_g1 = bulk_g1_gc_correction(
+            self.cn_s, self.cn_g1, input_col=self.input_col, gc_col=self.gc_col, cell_col=self.cell_col,
+            library_col=self.library_col, output_col=self.col2, device=device)
+        self.cn_s = normalize_by_cell(self.cn_s, self.cn_g1, input_col=self.col2, clone_col=self.clone_col,
+                                      temp_col=self.col3, output_col=self.rv_col, seg_col=self.col4,
+                                      cell_col=self.cell_col, chr_col=self.chr_col, start_col=self.start_col,
+                                      cn_state_col=self.cn_state_col, ploidy_col=self.ploidy_col, device=device)
+        # the reference names no cell column here (:199-202): the default
+        self.cn_s, self.manhattan_df = binarize_profiles(
+            self.cn_s, self.rv_col, rs_col=self.rs_col, frac_rt_col=self.frac_rt_col, thresh_col=self.col5,
+            MEAN_GAP_THRESH=0.7, EARLY_S_SKEW_THRESH=0.2, LATE_S_SKEW_THRESH=-0.2, device=device)
         return self.cn_s
 
     def _pert_model(self) -> pert_infer_scRT:
