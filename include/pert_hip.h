@@ -662,6 +662,51 @@ int pert_rt_tfs_hist(int32_t L, int32_t N, int32_t ldn, int32_t G, const uint8_t
                      const void* hours, const void* f10, const void* edges, int32_t n_edges, int32_t is_f64,
                      int32_t per_cell, uint32_t* hist_n, uint32_t* hist_rep, hipStream_t stream);
 
+/* ---- Cell bootstrap (cell_bootstrap.py): the two passes above for many resampled sets of cells at
+ * once.  A replicate is a weight per cell, w uint8 [rows][ldw] (how often the resampling picked the
+ * cell; ldw >= N a multiple of 16, the base 16-byte aligned, columns n >= N undefined and never
+ * counted).  rep follows the pert_rt_* conventions.  Integer adds only: results are exact, do not
+ * depend on the launch shape and repeat bit for bit.  Outputs are ADDED to; the caller zeroes them.
+ * PERT_E_ARG, before any launch, for a null or misaligned argument or a size outside the limits
+ * named below; nothing is written then. */
+#define PERT_TAG_BOOT 4u             /* the resampler's stream tag of THE COUNTER RULE (below) */
+#define PERT_BOOT_MAX_LAUNCH 65535   /* replicates of one pert_boot_weights call */
+
+/* The stratified resampler, replicates b0 .. b0 + Bc - 1.  Positions j = 0 .. N - 1 run over the
+ * cells sorted stably by stratum: order int32 [N] is the cell at each position, pos_lo / pos_n int32
+ * [N] the first position and the size of position j's stratum.  Draw (b, j) takes the 64-bit word
+ * (word 1 << 32 | word 0) of
+ *   philox(counter = {j, low half of b, PERT_TAG_BOOT, high half of b}, key of (seed, PERT_TAG_BOOT))
+ * and picks cell order[pos_lo[j] + mulhi64(word, pos_n[j])]; w[b - b0][n] = the number of draws of b
+ * that picked n, columns [N, ldw) zero.  No rejection loop; a draw depends only on seed, b, j and the
+ * stratum layout.  scratch uint32 [Bc][N] holds the counts before they are narrowed: zeroed by the
+ * caller, ADDED to.  *flag (uint32, zeroed by the caller) gets bit 0 when a count exceeds 255 (stored
+ * as 255) and bit 1 when pos_lo / pos_n / order do not describe strata of [0, N) (that draw is
+ * dropped).  Bc <= PERT_BOOT_MAX_LAUNCH. */
+int pert_boot_weights(int32_t N, int32_t ldw, const int32_t* pos_lo, const int32_t* pos_n, const int32_t* order,
+                      uint64_t seed, int64_t b0, int32_t Bc, uint32_t* scratch, uint8_t* w, uint32_t* flag,
+                      hipStream_t stream);
+
+/* count uint32 [C][L]: count[c][l] += sum_{n < N} wg[c][n] rep[l][n] for C weight rows, one per
+ * (replicate, group) and already masked by group (v_dot4_u32_u8 into 32-bit sums; an 8 x 8 tile of
+ * (weight row, bin) sums per lane, so a loaded rep fragment serves 8 weight rows and a weight
+ * fragment 8 bins).  N < 2^32 / 255 and L <= 8 * 65535. */
+int pert_boot_counts(int32_t L, int32_t N, int32_t ldn, const uint8_t* rep, int32_t C, int32_t ldw,
+                     const uint8_t* wg, uint32_t* count, hipStream_t stream);
+
+/* pert_rt_tfs_hist (per_cell 0) per group, for Bc replicates in one launch: hours is [Bc][G][L],
+ * f10 [N] and the edges as there; w uint8 [Bc][ldw] the replicates' weights (not masked: group does
+ * that).  For every replicate b, bin l and cell n < N with g = group[n] in [0, G) and w[b][n] > 0:
+ * t = hours[b][g][l] - f10[n], its interval i found by the routine of pert_rt_tfs_hist;
+ * hist_n[b][g][i] += w[b][n], and hist_rep[b][g][i] += w[b][n] where rep[l][n] is non-zero.
+ * hist_n / hist_rep are uint32 [Bc][G][n_edges - 1].  A workgroup reads its tile of rep once and
+ * walks the replicates over it.  G <= PERT_RT_MAX_GROUPS and n_edges <= PERT_RT_MAX_EDGES; the
+ * caller keeps L * sum_n w[b][n] < 2^32 for every b (a counter could wrap). */
+int pert_boot_tfs_hist(int32_t L, int32_t N, int32_t ldn, int32_t G, const uint8_t* rep, const int32_t* group,
+                       int32_t Bc, int32_t ldw, const uint8_t* w, const void* hours, const void* f10,
+                       const void* edges, int32_t n_edges, int32_t is_f64, uint32_t* hist_n, uint32_t* hist_rep,
+                       hipStream_t stream);
+
 /* ---- Per-cell quality features of the phase calls (phase_matrix.py; reference
  * predict_cycle_phase.py:23-88) on the decode's state matrices and the shard's reads, in place.
  * The series of cell n is column n of the matrix in row order, t = 0 .. L - 1; the lags are
@@ -713,7 +758,8 @@ int pert_phase_acf(int32_t L, int32_t N, int32_t ldn, const void* x, int32_t is_
  * simulated in several launches (cell0) get the numbers one launch over all of them gives.
  * A uniform is ((w >> 8) + 0.5) 2^-24 rounded to fp32 and kept below 1 (the one value that
  * rounds to 1.0 becomes 1 - 2^-24): strictly inside (0, 1).
- * (Tags 1 and 2 are the simulator's streams; 3 is PERT_TAG_DRAWS, pert_enum_draw.)
+ * (Tags 1 and 2 are the simulator's streams; 3 is PERT_TAG_DRAWS, pert_enum_draw; 4 is
+ * PERT_TAG_BOOT, pert_boot_weights, whose counter also carries the tag in the draw-round word.)
  * Stream PERT_SIM_TAG_CELLS (bin index 0): draw round 0 word 0 -> tau; draw round 1 + k words
  * 0, 1 -> beta k = mean + std sqrt(-2 ln u1) cos(2 pi u2), with u = ((w >> 8) + 0.5) 2^-24 and
  * the arithmetic in fp64, rounded to fp32 once.

@@ -28,6 +28,7 @@ TAG_DRAWS, MAX_DRAWS = 3, 4096             # pert_enum_draw: its stream tag, and
 PHASE_MAX_LAG = 64                         # pert_phase_counts / pert_phase_acf
 TAU_MAX_GRID = 1024                        # pert_tau_curve: the grid points of one call
 CPD_MAX_N = 10000                          # pert_cpd_search: the longest profile (PERT_CPD_MAX_N)
+TAG_BOOT, BOOT_MAX_LAUNCH = 4, 65535       # pert_boot_weights: its stream tag, and the replicates of one call
 
 # every symbol include/pert_hip.h declares
 EXPORTED_SYMBOLS = (
@@ -46,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "pert_enum_evidence", "pert_tau_curve", "pert_selftest_enum_evidence_host", "pert_selftest_tau_mix_host",
     "pert_lowess_workspace", "pert_lowess_curve", "pert_lowess_absmed",
     "pert_cpd_workspace", "pert_cpd_search",
+    "pert_boot_weights", "pert_boot_counts", "pert_boot_tfs_hist",
 )
 
 # include/pert_hip.h status codes of a sharded fit's communicator
@@ -274,6 +276,11 @@ def load(path: str, gil: bool = True):
     handle.pert_rt_counts.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_rt_tfs_hist.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i32, i32,
                                         i32, c_void_p, c_void_p, c_void_p]
+    handle.pert_boot_weights.argtypes = [i32, i32, c_void_p, c_void_p, c_void_p, c_uint64, i64, i32, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]
+    handle.pert_boot_counts.argtypes = [i32, i32, i32, c_void_p, i32, i32, c_void_p, c_void_p, c_void_p]
+    handle.pert_boot_tfs_hist.argtypes = [i32, i32, i32, i32, c_void_p, c_void_p, i32, i32, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, i32, i32, c_void_p, c_void_p, c_void_p]
     handle.pert_phase_counts.argtypes = [i32, i32, i32, i32, i64, c_void_p, c_void_p, i32, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     handle.pert_phase_acf_workspace.argtypes = [i32, i32, i32, POINTER(i64)]

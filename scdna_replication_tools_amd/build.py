@@ -25,10 +25,11 @@ SOURCES = [os.path.join(HERE, "csrc", "pert_kernels.hip"), os.path.join(HERE, "c
            os.path.join(HERE, "csrc", "sim_kernels.hip"), os.path.join(HERE, "csrc", "bin_kernels.hip"),
            os.path.join(HERE, "csrc", "post_kernels.hip"), os.path.join(HERE, "csrc", "ccc_kernels.hip"),
            os.path.join(HERE, "csrc", "phase_kernels.hip"), os.path.join(HERE, "csrc", "curve_kernels.hip"),
-           os.path.join(HERE, "csrc", "lowess_kernels.hip"), os.path.join(HERE, "csrc", "cpd_kernels.hip")]
+           os.path.join(HERE, "csrc", "lowess_kernels.hip"), os.path.join(HERE, "csrc", "cpd_kernels.hip"),
+           os.path.join(HERE, "csrc", "boot_kernels.hip")]
 DEPS = SOURCES + [os.path.join(HERE, "csrc", "pert_math.h"), os.path.join(HERE, "csrc", "sim_math.h"),
                   os.path.join(HERE, "csrc", "gmm2_stages.h"), os.path.join(HERE, "csrc", "enum_tile.h"),
-                  os.path.join(ROOT, "include", "pert_hip.h")]
+                  os.path.join(HERE, "csrc", "rt_interval.h"), os.path.join(ROOT, "include", "pert_hip.h")]
 OUT = os.path.join(HERE, "libpert_hip.so")
 OBJ_DIR = os.path.join(HERE, "build_obj")
 ARCH = os.environ.get("PERT_OFFLOAD_ARCH", "gfx950")

@@ -19,6 +19,7 @@
 // caller zeroes them (launches over cell or group subsets then sum by themselves).
 
 #include "../../include/pert_hip.h"
+#include "rt_interval.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -33,7 +34,8 @@ constexpr int kCountRows = 32;          // bins per tile of the counts kernel (8
 constexpr int kCountRPW = kCountRows / (kT / 64);
 constexpr int kCountCells = 64 * kCV;   // cells per workgroup of the counts kernel
 constexpr int kHistRows = 64;           // bins per tile of the histogram kernel (hours rows staged in LDS)
-constexpr int kEdgeSlots = 264;         // LDS slots of the edge table (>= 257, keeps what follows 16-byte aligned)
+using pert_rt::find_interval;           // rt_interval.h: shared with boot_kernels.hip
+using pert_rt::kEdgeSlots;
 constexpr int kTileCells = 64;          // cells per workgroup of the per-cell LDS tile
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
@@ -110,18 +112,6 @@ __global__ __launch_bounds__(kT) void rt_counts_kernel(int L, int N, int ldn, in
     const uint32_t c = s_cell[i];
     if (n < N && c != 0u) atomicAdd(&cell_count[n], c);
   }
-}
-
-// The interval i with edges[i] <= t < edges[i + 1], or -1 (t outside the edges, or NaN).
-// The scaled offset only chooses where the comparisons start.
-template <typename T>
-__device__ __forceinline__ int find_interval(T t, const T* s_edges, int nb, T e0, float inv_width) {
-  float q = (float)(t - e0) * inv_width;
-  q = fminf(fmaxf(q, 0.0f), (float)(nb - 1));           // fmaxf(NaN, 0) = 0
-  int i = (int)q;
-  while (i > 0 && t < s_edges[i]) --i;
-  while (i < nb - 1 && t >= s_edges[i + 1]) ++i;
-  return (t >= s_edges[i] && t < s_edges[i + 1]) ? i : -1;
 }
 
 // MODE 0: one histogram over all cells, privatised in LDS.  MODE 1: per-cell histograms, a

@@ -595,3 +595,9 @@ class RTMatrix:
     def twidth(self, curve='sigmoid', **kw):
         """calculate_twidth on ``tfs_histogram(**kw)``."""
         return twidth_from_points(*self.tfs_histogram(**kw), curve=curve)
+
+    def bootstrap(self, n_boot=200, seed=0, **kw):
+        """A ``CellBootstrap`` of this matrix (cell_bootstrap.py): the sampling spread over cells of
+        the pseudobulk profiles and of T-width."""
+        from .cell_bootstrap import CellBootstrap
+        return CellBootstrap(self, n_boot=n_boot, seed=seed, **kw)
